@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec (forward) of ViT-B/16 with a Switch-MoE MLP (E=8, top-1) in every block,
-224x224, batch 256 per GPU -- BASELINE.json configs[1] -- plus the roofline of the dominant hot-path kernel
-(the grouped expert GEMM) and the CPU oracle timed beside it.
+224x224, batch 256 per GPU -- BASELINE.json configs[1].  With --full, also the roofline of the dominant hot-path
+kernel (the grouped expert GEMM), the per-kernel table, the clock probe, the CPU oracle timed beside it, the parity
+checks and (expert parallel) the raw all-to-all rate.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          (no launcher: starts the N ranks itself as child processes and relays rank 0's line)
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's logits if --dump-outputs is given, and
+prints one JSON line; everything else it can measure runs only with --full.
 
 A step = one eval-mode forward of the whole model over one batch of synthetic images already resident in
 HBM (reference harness: engine.py:88-121 -- eval(), no_grad, fp16 autocast).  The MoE operator (router,
@@ -71,7 +75,38 @@ def parse():
                          "opt-in, single rank only)")
     ap.add_argument("--force-ep", action="store_true",
                     help="diagnostic: drive the expert-parallel code path on one GPU (world of one rank)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times and the roofline (HIP events in the timed "
+                         "region, extra profiled steps, the clock probe), the CPU baseline, the parity checks against the oracle and "
+                         "(expert parallel) the raw all-to-all rate; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits of the last timed step as DIR/logits.npy (float32; "
+                         "DIR/logits_rank<r>.npy per rank when N > 1)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # all ranks' dumped arrays together
+
+
+def dump_outputs(dirname, logits, world, rank):
+    """The last timed step's logits -> DIR/<name>.npy in float32.  An output larger than this rank's share of the budget is
+    cut to a fixed, evenly strided sample of its rows (the same rows for the same arguments)."""
+    import numpy as np
+
+    arr = logits.detach().float().cpu().numpy()
+    arr = arr.reshape(arr.shape[0], -1)
+    row_bytes = max(1, arr.shape[1] * 4)
+    keep = max(1, (DUMP_BUDGET_BYTES // world) // row_bytes)
+    if arr.shape[0] > keep:
+        arr = arr[:: -(-arr.shape[0] // keep)]
+    os.makedirs(dirname, exist_ok=True)
+    name = "logits" if world == 1 else f"logits_rank{rank}"
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def build_model(args, world, rank, device):
@@ -108,7 +143,7 @@ def build_model(args, world, rank, device):
     model.ep_micro_batches = max(1, args.ep_micro_batches)
     model.compute_streams = args.compute_streams if world == 1 else 1
     sd_cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and getattr(args, "full", False) and not args.no_cpu_baseline:
         sd_cpu = {k: v.detach().clone() for k, v in model.state_dict().items()}
     return model.to(device).eval(), sd_cpu
 
@@ -315,36 +350,41 @@ def main():
         else:
             step()
     fence()
-    # Per-launch HIP events inside the timed region: the roofline kernel only (two event records around each of the
+    # --full: per-launch HIP events inside the timed region, the roofline kernel only (two event records around each of the
     # ~110 other launches of a step cost ~0.5 ms per step).  The other kernels' table comes from a few extra,
     # untimed steps below.
-    ops.profile_begin({"grouped_gemm", "expert_ffn"})
+    if args.full:
+        ops.profile_begin({"grouped_gemm", "expert_ffn"})
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step times (median reported)
     t0 = time.perf_counter()
     marks[0].record()
     ep_overflow_in_timed_region = False
+    logits = None
     for i in range(args.steps):
         if ep_static:
             try:
-                step()
+                logits = step()
             except _ep.StaticExchangeOverflow:      # raised by every rank at the same exchange (the deferred watch inside the forward):
                 ep_overflow_in_timed_region = True  # the step is repeated on the counted exchange INSIDE the timed region, and the
                 with _ep.dynamic_only():            # line says so (it cannot happen with one fixed batch whose routing fitted in warm-up)
-                    step()
+                    logits = step()
         else:
-            step()
+            logits = step()
         marks[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
-    prof = ops.profile_end()
+    prof = ops.profile_end() if args.full else []
     if ep_static:
         try:     # the timed steps ran without reading their overflow reports (no host sync): read them now
             _ep.check_static_overflow(flush=True)
         except _ep.StaticExchangeOverflow:
             ep_overflow_in_timed_region = True      # the timed outputs are void: the line says so
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, logits, world, rank)
+    del logits
     side_steps = 0
-    if world == 1 and not args.force_ep:
+    if args.full and world == 1 and not args.force_ep:
         side_steps = max(1, min(5, args.steps))
         ops.profile_begin()
         for _ in range(side_steps):
@@ -358,7 +398,7 @@ def main():
 
     # ---- expert parallel: the raw exchange beside the step (a2a GB/s per link vs the 153 GB/s link) ---
     ep_info = None
-    if world > 1:
+    if args.full and world > 1:
         rows = (args.batch * 197 // world) * world          # equal splits: the average layer's volume
         sbuf = torch.randn(rows, 768, device=device).half()
         rbuf = torch.empty_like(sbuf)
@@ -528,14 +568,15 @@ def main():
                                    f"full eval forward (12 blocks: attention + MoE MLP), fp16 autocast",
                        "global_batch": args.batch * world, "tokens_per_image": 197, "compute_streams": args.compute_streams,
                        "parallelism": ("single" if not args.force_ep else f"single (EP code path forced, {'speculative static' if ep_static else 'counted'} exchange, {args.ep_micro_batches} interleaved micro-batches x {args.ep_chunks} chunks per layer)") if world == 1 else f"ep{world} (experts/{world} per rank, {'speculative static' if ep_static else 'counted'} all-to-all, {args.ep_micro_batches} interleaved micro-batches x {args.ep_chunks} chunks per layer)"},
-            "roofline": roofline,
-            "kernels": kernels,
         }
-        hot = ("router", "ln_router", "plan", "scatter", "combine", "combine_ln", "grouped_gemm")  # the MoE operator's own kernels ("grouped_gemm" includes the fused launches)
-        moe_ms = sum(a["ms"] / (args.steps if n.startswith("grouped_gemm") else max(1, side_steps))
-                     for n, a in agg.items() if n in hot)
-        out["hot_path"] = {"moe_kernels_ms_per_step": round(moe_ms, 3),
-                           "share_of_step": round(moe_ms / (elapsed / args.steps * 1e3), 3)}
+        if args.full:
+            out["roofline"] = roofline
+            out["kernels"] = kernels
+            hot = ("router", "ln_router", "plan", "scatter", "combine", "combine_ln", "grouped_gemm")  # the MoE operator's own kernels ("grouped_gemm" includes the fused launches)
+            moe_ms = sum(a["ms"] / (args.steps if n.startswith("grouped_gemm") else max(1, side_steps))
+                         for n, a in agg.items() if n in hot)
+            out["hot_path"] = {"moe_kernels_ms_per_step": round(moe_ms, 3),
+                               "share_of_step": round(moe_ms / (elapsed / args.steps * 1e3), 3)}
         if ep_info is not None:
             out["expert_parallel"] = ep_info
         if world == 1 and sd_cpu is not None:

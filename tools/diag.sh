@@ -63,7 +63,7 @@ case "$cmd" in
       for nb in 0 default; do
         if [ $nb = default ]; then unset SMOE_PS_NBLOCK; else export SMOE_PS_NBLOCK=$nb; fi
         echo "== SMOE_PS_NBLOCK=$nb (repeat $rep)" >> $O
-        python3 bench.py --no-cpu-baseline --clock-seconds 0 2>/dev/null | tail -1 | python3 -c "
+        python3 bench.py --full --no-cpu-baseline --clock-seconds 0 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print(d['ms_per_step'], {k: v['avg_ms'] for k, v in d['kernels'].items() if 'gemm' in k or 'ffn' in k})" >> $O

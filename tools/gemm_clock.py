@@ -9,7 +9,7 @@ clock = d(s_memtime) / d(s_memrealtime) x 100 MHz, median over workgroups.  Prin
     {"gemm1_mhz": ..., "gemm2_mhz": ..., "fused_mhz": ..., "gemm1_ms": ..., "gemm2_ms": ..., "fused_ms": ..., "seconds_each": ..., ...}
 (fused = smoe_expert_ffn, both GEMMs in one persistent launch)
 
-bench.py starts it as a child process (SLIMMOE_LIB selects the library at import) and reports `frac_of_clocked_peak` from it.
+bench.py --full starts it as a child process (SLIMMOE_LIB selects the library at import) and reports `frac_of_clocked_peak` from it.
 usage: SLIMMOE_LIB=slim-switch-moe-vit_amd/libslimmoe_hip_clock.so python3 tools/gemm_clock.py [seconds_each=2.0] [batch=256]"""
 import ctypes
 import json
