@@ -493,6 +493,14 @@ int smoe_adamw_step_multi(const int64_t* tab, const float* hyp, int n_tensors, c
 int smoe_amp_update(float* scale, float* growth_tracker, const float* found_inf, float growth_factor, float backoff_factor,
                     int growth_interval, void* stream);
 int smoe_step_advance(float* step, const float* found_inf, void* stream);
+/* Weight EMA of the model (timm.utils.ModelEma.update, engine.py:77-78: `ema_v.copy_(ema_v * decay + (1. - decay) * model_v)`),
+ * every tensor in ONE launch, in place.  tab = int64 [3][n_tensors] in device memory: rows ema, model (addresses of f32 tensors,
+ * 16-byte aligned) and n (elements, 0 allowed); blk = int32 [2][n_blocks] as for smoe_adamw_step_multi.  Per element
+ * ema = (ema * decay) + (model * one_minus_decay), three separately rounded f32 operations -- bit-equal to torch's line when the
+ * caller passes f32(decay) and f32(1 - decay) with the difference taken in double (for 0.99996 that is not 1.0f - f32(decay)).
+ * skip (may be NULL): a device f32 flag; non-zero = the launch writes nothing.  No allocation, no synchronisation.          */
+int smoe_ema_update_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, float decay,
+                          float one_minus_decay, const float* skip, void* stream);
 
 /* ---- small helpers ------------------------------------------------------------------------------------
  * elementwise cast between dtypes (weight shadow copies; not on the per-step path)                  */

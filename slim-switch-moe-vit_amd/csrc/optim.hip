@@ -8,6 +8,7 @@
 //                       a device-side multiplier (inv_scale x clip coefficient); skipped entirely when found_inf is set;
 //                       the step count lives on the device (no host sync anywhere in the step)
 //   smoe_amp_update   : GradScaler.update() (growth / backoff of the loss scale) + the optimizer's step counter
+//   smoe_ema_update_multi : the weight EMA after the step (timm ModelEma.update), every tensor in one launch, skippable from the device
 #include "smoe_common.h"
 #include <type_traits>
 
@@ -164,6 +165,54 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_multi_kernel(const int64_t*
                   shadow ? (int)shadow[(int64_t)n_t + t] : SMOE_F16);
 }
 
+// weight EMA (timm.utils.ModelEma.update: `ema_v.copy_(ema_v * decay + (1. - decay) * model_v)`, engine.py:77-78), in place.
+// tab = int64 [3][n_t]: rows ema, model (addresses, f32) and n; blk as above.  Bit-equal to torch's line: three separately
+// rounded f32 operations with the two host-side factors f32(decay) and f32(1 - decay) (the latter computed in double) -- the
+// _rn intrinsics keep -ffp-contract=on from fusing them into an FMA.
+__global__ __launch_bounds__(OPT_THREADS) void ema_update_multi_kernel(const int64_t* __restrict__ tab, int n_t,
+                                                                       const int32_t* __restrict__ blk, int64_t n_blocks,
+                                                                       float decay, float one_minus_decay,
+                                                                       const float* __restrict__ skip) {
+  if (skip && *skip != 0.f) return;
+  const int t = blk[blockIdx.x];
+  if (t < 0 || t >= n_t) return;   // the table is caller data
+  float* __restrict__ e = reinterpret_cast<float*>(tab[t]);
+  const float* __restrict__ m = reinterpret_cast<const float*>(tab[(int64_t)n_t + t]);
+  const int64_t n = tab[2ll * n_t + t];
+  const int64_t base = (int64_t)blk[n_blocks + blockIdx.x] * SUMSQ_BLOCK;
+  if (base + SUMSQ_BLOCK <= n) {
+    // a whole block: 16 x 16 bytes of each tensor per thread, loads issued EMA_UNROLL vectors at a time (more bytes in flight)
+    constexpr int EMA_UNROLL = 4;
+    for (int k = 0; k < SUMSQ_BLOCK / (OPT_THREADS * 4); k += EMA_UNROLL) {
+      f32x4 ev[EMA_UNROLL], mv[EMA_UNROLL];
+#pragma unroll
+      for (int u = 0; u < EMA_UNROLL; ++u) {
+        const int64_t i = base + (int64_t)(k + u) * OPT_THREADS * 4 + threadIdx.x * 4;
+        ev[u] = *reinterpret_cast<const f32x4*>(e + i);
+        mv[u] = *reinterpret_cast<const f32x4*>(m + i);
+      }
+#pragma unroll
+      for (int u = 0; u < EMA_UNROLL; ++u) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ev[u][q] = __fadd_rn(__fmul_rn(ev[u][q], decay), __fmul_rn(mv[u][q], one_minus_decay));
+        *reinterpret_cast<f32x4*>(e + base + (int64_t)(k + u) * OPT_THREADS * 4 + threadIdx.x * 4) = ev[u];
+      }
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x * 4; i < n; i += OPT_THREADS * 4) {   // the tensor's last, partial block
+    if (i + 4 <= n) {
+      f32x4 ev = *reinterpret_cast<const f32x4*>(e + i);
+      const f32x4 mv = *reinterpret_cast<const f32x4*>(m + i);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ev[q] = __fadd_rn(__fmul_rn(ev[q], decay), __fmul_rn(mv[q], one_minus_decay));
+      *reinterpret_cast<f32x4*>(e + i) = ev;
+    } else {
+      for (int64_t j = i; j < n; ++j) e[j] = __fadd_rn(__fmul_rn(e[j], decay), __fmul_rn(m[j], one_minus_decay));
+    }
+  }
+}
+
 __global__ void amp_update_kernel(float* scale, float* growth_tracker, const float* found_inf, float growth, float backoff,
                                   float interval) {
   if (found_inf && *found_inf != 0.f) {
@@ -269,5 +318,16 @@ extern "C" int smoe_adamw_step_multi(const int64_t* tab, const float* hyp, int n
     default: hipLaunchKernelGGL(adamw_multi_kernel<bf16_bits>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, eps, step, grad_mult, found_inf, shadow); break;
   }
   SMOE_CHECK_LAUNCH("smoe_adamw_step_multi");
+  return 0;
+}
+
+extern "C" int smoe_ema_update_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, float decay,
+                                     float one_minus_decay, const float* skip, void* stream) {
+  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31), "smoe_ema_update_multi: bad arguments");
+  if (n_blocks == 0) return 0;
+  SMOE_REQUIRE(tab && blk, "smoe_ema_update_multi: null pointer");
+  hipLaunchKernelGGL(ema_update_multi_kernel, dim3((unsigned)n_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, tab, n_tensors,
+                     blk, n_blocks, decay, one_minus_decay, skip);
+  SMOE_CHECK_LAUNCH("smoe_ema_update_multi");
   return 0;
 }

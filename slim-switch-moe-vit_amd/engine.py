@@ -239,13 +239,19 @@ class GraphedTrainStep:
     per-step scheduler the harness gives up and runs eagerly).  After the last replay -- ``finish()`` -- every parameter's version
     counter is bumped: the captured kernels refreshed the 16-bit weight images in place, but images that the FORWARD re-derives (the
     transposed dgrad operands) were made before the last update, and host-side version counters do not move under a replay.
-    Host-side counters the kernels cannot keep (``Gate._total_tokens``) are advanced by hand."""
+    Host-side counters the kernels cannot keep (``Gate._total_tokens``) are advanced by hand.
+
+    With this package's ``optim.ModelEma`` (its tensors on the model's device) the step ends with the EMA update -- one launch, skipped
+    on the device when the step's loss is non-finite -- and is captured with it; the decay counts as a host hyper-parameter, and
+    ``finish()`` bumps the EMA model's version counters as well (its 16-bit images are re-cast on its next forward).  Any other EMA
+    object keeps the step eager."""
 
     WARM = 3
 
-    def __init__(self, model, criterion, optimizer, loss_scaler, max_norm, with_inputs, aux_loss_weight, autocast):
+    def __init__(self, model, criterion, optimizer, loss_scaler, max_norm, with_inputs, aux_loss_weight, autocast, model_ema=None):
         from .fmoe import FMoETransformerMLP
         self.model, self.criterion, self.optimizer, self.scaler = model, criterion, optimizer, loss_scaler
+        self.model_ema = model_ema
         self.max_norm, self.with_inputs, self.aux_w, self.autocast = max_norm, with_inputs, aux_loss_weight, autocast
         self.moes = [m for m in model.modules() if isinstance(m, FMoETransformerMLP)]
         self.gates = [m for m in model.modules() if hasattr(m, "_total_tokens") and hasattr(m, "skip_counter")]
@@ -257,8 +263,15 @@ class GraphedTrainStep:
         """``ep_graph``: whether an expert-parallel model may be captured (train_one_epoch: a group of ONE rank, or hip_graph=True).
         It can be when the step has no host round trip: every expert-parallel layer a CAPACITY gate on the static exchange (its slots
         cannot overflow and a fixed batch shape cannot outgrow the agreed row count) with the collectives on the compute stream."""
-        from .optim import NativeScaler as _OwnScaler
+        from .optim import ModelEma, NativeScaler as _OwnScaler
         dev = torch.device(device)
+        if model_ema is not None:
+            # on the MODEL's device: `device` may name no index (the reference passes torch.device("cuda")), a tensor's always does
+            mdev = next(iter(model.parameters()), None)
+            mdev = None if mdev is None else mdev.device
+            if not (isinstance(model_ema, ModelEma) and mdev is not None and mdev.type == "cuda"
+                    and all(t.device == mdev for t in model_ema.tensors())):
+                return False
         mods = [m for m in model.modules() if hasattr(m, "ep_active") and m.ep_active()]
         if mods:
             from . import ep
@@ -267,12 +280,13 @@ class GraphedTrainStep:
                     and all(m.gate.capacity(1 << 20) >= 0 and ep.static_kind(m, m.compute_dtype or default_compute_dtype()) == "capacity"
                             for m in mods)):
                 return False
-        return (dev.type == "cuda" and model_ema is None and getattr(optimizer, "_slimmoe_refreshes_images", False)
+        return (dev.type == "cuda" and getattr(optimizer, "_slimmoe_refreshes_images", False)
                 and isinstance(loss_scaler, _OwnScaler) and loss_scaler.enabled
                 and not getattr(optimizer, "is_second_order", False))
 
     def _hyper(self):
-        return tuple((g.get("lr"), g.get("weight_decay"), tuple(g.get("betas", ())), g.get("eps")) for g in self.optimizer.param_groups)
+        return (tuple((g.get("lr"), g.get("weight_decay"), tuple(g.get("betas", ())), g.get("eps")) for g in self.optimizer.param_groups),
+                None if self.model_ema is None else self.model_ema.decay)
 
     def eager(self, samples, targets):
         """The step itself (also what gets captured).  Returns the detached f32 loss."""
@@ -287,6 +301,8 @@ class GraphedTrainStep:
         lv = loss.detach().float()
         self.optimizer.zero_grad()
         self.scaler(loss, self.optimizer, clip_grad=self.max_norm, parameters=self.model.parameters(), create_graph=False)
+        if self.model_ema is not None:     # (a non-finite loss: the scaler skipped the step, and the EMA stays as it is)
+            self.model_ema.update(self.model, skip=(~torch.isfinite(lv)).to(torch.float32))
         return lv
 
     def _capture(self, samples, targets):
@@ -346,7 +362,8 @@ class GraphedTrainStep:
         """Call when the replays end (end of the epoch, or before an eager step): host-side version counters catch up."""
         if self.replayed:
             from .optim import _bump_versions
-            _bump_versions([p for group in self.optimizer.param_groups for p in group["params"]])
+            _bump_versions([p for group in self.optimizer.param_groups for p in group["params"]]
+                           + ([] if self.model_ema is None else self.model_ema.tensors()))
             self.replayed = False
 
 
@@ -371,15 +388,17 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
     parameters in the reference's order (main.py:825-838 calls it positionally: ``model_ema`` and ``mixup_fn`` sit in
     positions 9 and 10): autocast forward, criterion, ``loss_scaler(loss, optimizer, clip_grad=max_norm,
     parameters=model.parameters())`` (optim.NativeScaler keeps the whole step on the device), ``model_ema.update(model)``
-    after every step and ``mixup_fn(samples, targets)`` before it when given, ``args.bce_loss`` as at engine.py:49-50.
+    after every step (``optim.ModelEma``: one launch, captured with the step under ``hip_graph``) and ``mixup_fn(samples,
+    targets)`` before it when given, ``args.bce_loss`` as at engine.py:49-50.
     ``max_norm=None`` = no clipping (what main.py passes by default, ``--clip-grad None``).  A criterion whose forward takes
     three tensors is called like the reference's DistillationLoss, ``criterion(samples, outputs, targets)``.
 
     Keyword-only extensions: ``aux_loss_weight`` adds the MoE gates' load-balance losses (SwitchGate, BASELINE cfg 5);
     ``gate_delta`` runs the token-skip gates' threshold schedule (``Gate.step(delta)`` for every gate, as main.py:887-891
     does after the epoch's steps); ``autocast``; ``hip_graph`` (default False; True, or "auto" = SLIMMOE_TRAIN_GRAPH=1): the whole step
-    replayed from one HIP graph per batch shape (GraphedTrainStep: needs this package's AdamW + NativeScaler, one rank, no EMA; 2 x on
-    the reference's DeiT-Tiny model, nothing on ViT-B) -- anything it cannot take runs eagerly, as before; ``ep_speculative`` (under
+    replayed from one HIP graph per batch shape (GraphedTrainStep: needs this package's AdamW + NativeScaler, one rank, no EMA
+    other than an ``optim.ModelEma`` on the model's device; 2 x on the reference's DeiT-Tiny model, nothing on ViT-B) -- anything
+    it cannot take runs eagerly, as before; ``ep_speculative`` (under
     expert parallelism; alpha, "auto" = SLIMMOE_EP_ALPHA, None / 0 = off): gates WITHOUT a capacity (the reference's NaiveGate) train on
     the speculative static exchange -- no host round trip per layer; the forward's overflow report is read once, before the backward,
     and a forward whose routing did not fit its slots is repeated on the counted exchange by all ranks together (capacity gates are on
@@ -388,10 +407,11 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
     The reference aborts on a non-finite loss by reading ``loss.item()`` in every step (engine.py:56-60: one host sync per
     step), BEFORE the optimizer step and the EMA update.  Here the check is a device-side count read every ``check_every`` steps
     (default 50) and at the end of the epoch: the same abort (``SystemExit(1)`` after the message), at most ``check_every`` steps
-    late.  What runs meanwhile is gated: an enabled ``optim.NativeScaler`` skips the update on a non-finite gradient by itself; with any
-    other (or a disabled) scaler, or with a ``model_ema`` (whose update is a host call that cannot be skipped from the device), the loss is read
-    in EVERY step, as the reference does, so no weight, EMA or checkpoint ever absorbs a non-finite step.  The metric logger is
-    driver plumbing (out of scope).
+    late.  What runs meanwhile is gated: an enabled ``optim.NativeScaler`` skips the update on a non-finite gradient by itself, and an
+    ``optim.ModelEma`` is updated with ``skip=<the loss is non-finite>`` (a device flag: a step whose gradients overflowed but whose loss
+    is finite still moves the EMA, as the reference's unconditional update does); with any other (or a disabled) scaler, or with any
+    other ``model_ema`` (whose update is a host call that cannot be skipped from the device), the loss is read in EVERY step, as the
+    reference does, so no weight, EMA or checkpoint ever absorbs a non-finite step.  The metric logger is driver plumbing (out of scope).
     Returns {"loss": mean loss, "steps": n, "lr": first group's lr}."""
     from .fmoe import FMoETransformerMLP
     from .resmoe import Gate
@@ -401,8 +421,9 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
     moes = [m for m in model.modules() if isinstance(m, FMoETransformerMLP)]
     with_inputs = _criterion_takes_inputs(criterion)
     _size_static_exchange(model, data_loader)
-    from .optim import NativeScaler as _OwnScaler
-    every_step = model_ema is not None or not (isinstance(loss_scaler, _OwnScaler) and loss_scaler.enabled)
+    from .optim import ModelEma, NativeScaler as _OwnScaler
+    every_step = ((model_ema is not None and not isinstance(model_ema, ModelEma))
+                  or not (isinstance(loss_scaler, _OwnScaler) and loss_scaler.enabled))
     if every_step:
         check_every = 1
     bce = bool(getattr(args, "bce_loss", False)) if args is not None else False
@@ -413,7 +434,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
         import os
         hip_graph = os.environ.get("SLIMMOE_TRAIN_GRAPH", "0") == "1"
     if hip_graph and not every_step and GraphedTrainStep.supported(model, optimizer, loss_scaler, dev, model_ema, ep_graph):
-        graphed = GraphedTrainStep(model, criterion, optimizer, loss_scaler, max_norm, with_inputs, aux_loss_weight, autocast)
+        graphed = GraphedTrainStep(model, criterion, optimizer, loss_scaler, max_norm, with_inputs, aux_loss_weight, autocast,
+                                   model_ema=model_ema)
     from . import ep as _ep
     ep_spec, ep_repeats = False, 0
     if any(m.ep_active() for m in _ep._ep_modules(model)):
@@ -465,10 +487,14 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
             optimizer.zero_grad()
             is_second_order = hasattr(optimizer, "is_second_order") and optimizer.is_second_order
             loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters(), create_graph=is_second_order)
+            nonfinite = (~finite).to(bad.dtype)
             if model_ema is not None:
-                model_ema.update(model)
+                if every_step:                            # (the loss was read above)
+                    model_ema.update(model)
+                else:                                     # optim.ModelEma: skipped on the device when the loss is not finite
+                    model_ema.update(model, skip=nonfinite)
             loss_sum += torch.where(finite, lv, torch.zeros_like(lv))
-            bad += (~finite).to(bad.dtype)
+            bad += nonfinite
             n += 1
             if check_every > 1 and n % check_every == 0 and int(bad):
                 print(f"Loss is non-finite in {int(bad)} of {n} steps, stopping training")

@@ -15,6 +15,10 @@ scale, the non-finite flag, the clip coefficient and the step count all living o
 
 ``AdamW`` and ``NativeScaler`` keep the call signatures, ``state_dict`` keys and numerics of what they replace; CPU
 tensors (and non-f32 parameters) fall back to the torch composition, which is also what the tests compare against.
+
+``ModelEma`` is ``timm.utils.ModelEma`` (the reference trains with ``--model-ema`` on: main.py:81-84, 599-606; engine.py:77-78) with
+its per-step update -- four torch launches per state-dict entry upstream -- as ONE launch of ``smoe_ema_update_multi``, bit-equal to
+timm's line and skippable from the device, so that the graphed training step can capture it.
 """
 from __future__ import annotations
 
@@ -410,3 +414,188 @@ class NativeScaler:
         else:
             self._scale *= self.backoff_factor
             self._growth_tracker.zero_()
+
+
+# -- weight EMA -----------------------------------------------------------------------------------------------------------------
+# module attributes that hold per-process GPU plumbing rather than model state: an EMA copy starts without them (re-made lazily)
+_TRANSIENT_ATTRS = ("_side_streams", "_ep_static_agreed", "_ep_slots", "_ep_last_stats")
+
+
+def _independent_copy(model: torch.nn.Module) -> torch.nn.Module:
+    """``copy.deepcopy(model)`` whose derived-tensor caches are its OWN and empty.  A plain deepcopy would carry the original's
+    ``StreamCache`` objects over -- 16-bit weight images, zero-row constants, the events behind them -- as copies that no
+    ``invalidate_weight_images()`` reaches (they are not in ``_cache._ALL``).  Each cache of the original is mapped to a fresh one of
+    the same class (the load_state_dict post-hooks that invalidate it find it under the same attribute); the side streams and the
+    exchange state are left out (made again on first use)."""
+    import copy
+    from ._cache import StreamCache
+    memo = {}
+    for m in model.modules():
+        for k, v in m.__dict__.items():
+            if isinstance(v, StreamCache):
+                memo[id(v)] = type(v)()
+            elif k in _TRANSIENT_ATTRS:
+                memo[id(v)] = None
+    ema = copy.deepcopy(model, memo)
+    for m in ema.modules():
+        for k in _TRANSIENT_ATTRS:
+            if k in m.__dict__ and m.__dict__[k] is None:
+                del m.__dict__[k]
+    return ema
+
+
+def _ema_kernel_ok(e: torch.Tensor, m: torch.Tensor) -> bool:
+    return (e.is_cuda and e.dtype == torch.float32 and m.dtype == torch.float32 and m.device == e.device and e.shape == m.shape
+            and e.is_contiguous() and m.is_contiguous() and e.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0)
+
+
+class ModelEma:
+    """``timm.utils.ModelEma`` (timm 0.4 / 0.5; main.py:599-606, engine.py:77-78) with the update in ONE HIP launch.
+
+    ``ModelEma(model, decay=0.9999, device='', resume='')``: ``.ema`` is an independent copy of ``model`` (eval mode, no grad, its own
+    empty weight-image caches), kept on ``device`` when that is given (``'cpu'``: ``--model-ema-force-cpu``).  ``update(model)``
+    applies timm's ``ema_v.copy_(ema_v * decay + (1. - decay) * model_v)`` to every ``state_dict()`` entry of the EMA (buffers too),
+    in ``ema.state_dict()`` order, reading a DataParallel / DDP-wrapped ``model`` under its ``module.`` keys as timm does.  f32 device
+    entries go through ``smoe_ema_update_multi`` -- one launch, bit-equal to torch's line, no host-to-device copy once the pointer
+    table is cached, so it can be captured (engine.GraphedTrainStep); everything else (CPU, 16-bit, integer or mismatched entries, and
+    tied weights: one storage under several keys, which timm updates once per key) takes timm's line itself.  Keyword-only ``skip``: a device f32 flag; non-zero = this update changes nothing (the harness passes
+    "the loss was non-finite" without asking the host).
+
+    Checkpoints: ``_load_checkpoint(path_or_file)`` reads ``state_dict_ema`` (utils._load_checkpoint_for_ema hands it a BytesIO);
+    ``state_dict()`` / ``load_state_dict()`` are the unwrapped EMA model's, so ``timm.utils.get_state_dict(model_ema)`` works unchanged
+    (this class deliberately has no ``.module``).  Expert-parallel models are refused."""
+
+    def __init__(self, model: torch.nn.Module, decay: float = 0.9999, device="", resume: str = ""):
+        ep = [n for n, m in model.named_modules() if callable(getattr(m, "ep_active", None)) and m.ep_active()]
+        if ep:
+            raise ValueError(f"ModelEma: expert-parallel MoE layers ({', '.join(ep[:3])}{', ...' if len(ep) > 3 else ''}) are not "
+                             "supported: their experts are rank-private and the copy would share the communicator state")
+        self.ema = _independent_copy(model)
+        self.ema.eval()
+        self.decay = decay
+        self.device = device
+        if device:
+            self.ema.to(device=device)
+        self.ema_has_module = hasattr(self.ema, "module")
+        self._tables = {}      # device -> (entry key, device table, blk, blocks): the kernel's pointer table
+        self._captured = []    # tables a captured graph launches with: kept alive as long as this object
+        if resume:
+            self._load_checkpoint(resume)
+        for p in self.ema.parameters():
+            p.requires_grad_(False)
+
+    def _unwrapped(self) -> torch.nn.Module:
+        return self.ema.module if self.ema_has_module else self.ema
+
+    def _load_checkpoint(self, checkpoint_path) -> None:
+        from collections import OrderedDict
+        import logging
+        checkpoint = torch.load(checkpoint_path, map_location="cpu")
+        assert isinstance(checkpoint, dict)
+        if "state_dict_ema" in checkpoint:
+            new_state_dict = OrderedDict()
+            for k, v in checkpoint["state_dict_ema"].items():
+                # ema model may have been wrapped by DataParallel, and need module prefix
+                if self.ema_has_module:
+                    name = "module." + k if not k.startswith("module") else k
+                else:
+                    name = k
+                new_state_dict[name] = v
+            self.ema.load_state_dict(new_state_dict)
+            logging.getLogger(__name__).info("Loaded state_dict_ema")
+        else:
+            logging.getLogger(__name__).warning("Failed to find state_dict_ema, starting from loaded model weights")
+
+    def state_dict(self, *args, **kwargs):
+        return self._unwrapped().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        return self._unwrapped().load_state_dict(state_dict, strict=strict)
+
+    def tensors(self):
+        """The EMA model's parameters and buffers (what ``update`` writes)."""
+        return list(self.ema.parameters()) + list(self.ema.buffers())
+
+    @torch.no_grad()
+    def update(self, model: torch.nn.Module, *, skip: Optional[torch.Tensor] = None) -> None:
+        needs_module = hasattr(model, "module") and not self.ema_has_module
+        msd = model.state_dict()
+        entries = []
+        for k, ema_v in self.ema.state_dict().items():
+            if needs_module:
+                k = "module." + k
+            model_v = msd[k].detach()
+            if self.device:
+                model_v = model_v.to(device=self.device)
+            entries.append((ema_v, model_v))
+        # an EMA storage under two keys (tied weights) gets timm's line once per key, one after the other: such entries take the torch
+        # path in state-dict order (inside one launch, two workgroups would read and write the same memory at the same time)
+        owners = {}
+        for ema_v, _ in entries:
+            if ema_v.numel():
+                s = (ema_v.device, ema_v.untyped_storage().data_ptr())
+                owners[s] = owners.get(s, 0) + 1
+        fused, rest = {}, []
+        for ema_v, model_v in entries:
+            shared = ema_v.numel() and owners[(ema_v.device, ema_v.untyped_storage().data_ptr())] > 1
+            if not shared and _ema_kernel_ok(ema_v, model_v):
+                fused.setdefault(ema_v.device, []).append((ema_v, model_v))
+            else:
+                rest.append((ema_v, model_v))
+        for dev, pairs in fused.items():
+            self._launch(dev, pairs, skip)
+        keep = {}      # device -> the skip flag as a bool there (one copy per device, not one per entry)
+        for ema_v, model_v in rest:        # timm's line
+            new = ema_v * self.decay + (1. - self.decay) * model_v
+            if skip is not None:
+                if ema_v.device not in keep:
+                    keep[ema_v.device] = skip.to(ema_v.device).reshape(()) != 0
+                new = torch.where(keep[ema_v.device], ema_v, new)
+            ema_v.copy_(new)
+        if fused:
+            # the kernel wrote through raw pointers: move the version counters, so that the EMA model's 16-bit weight images are
+            # re-cast on its next forward (state_dict() entries share their parameter's counter)
+            _bump_versions([e for pairs in fused.values() for e, _ in pairs])
+
+    def _launch(self, dev, pairs, skip) -> None:
+        key = tuple((e.data_ptr(), m.data_ptr(), e.numel()) for e, m in pairs)
+        hit = self._tables.get(dev)
+        if hit is None or hit[0] != key:
+            hit = (key,) + _ema_table(pairs, dev)
+            if not torch.cuda.is_current_stream_capturing():   # (a table made inside a capture lives in the graph's pool)
+                self._tables[dev] = hit
+        if torch.cuda.is_current_stream_capturing():
+            self._captured.append(hit)
+        _ema_launch(hit[1:], len(pairs), self.decay, skip)
+
+
+def _ema_table(pairs, dev):
+    """(tab int64 [3][n_t]: ema, model, n; blk; number of blocks) of smoe_ema_update_multi on the device."""
+    blk, nb = _block_table([e.numel() for e, _ in pairs], dev)
+    tab = _pointer_table([[e.data_ptr() for e, _ in pairs], [m.data_ptr() for _, m in pairs], [e.numel() for e, _ in pairs]], dev)
+    return tab, blk, sum(nb)
+
+
+def _ema_launch(table, n_tensors: int, decay: float, skip: Optional[torch.Tensor]) -> None:
+    tab, blk, n_blocks = table
+    if skip is not None:
+        assert skip.device == tab.device and skip.dtype == torch.float32 and skip.numel() == 1, "skip is a device f32 flag"
+    decay = float(decay)
+    # the factors torch's `ema * decay + (1. - decay) * model` multiplies by: f32(decay) and f32(1 - decay), the difference in double
+    rc = _lib.load().smoe_ema_update_multi(tab.data_ptr(), n_tensors, blk.data_ptr(), n_blocks, decay, 1.0 - decay, ops._ptr(skip),
+                                           ops._stream(tab))
+    _lib.check(rc, "smoe_ema_update_multi")
+
+
+@torch.no_grad()
+def ema_update_(emas, models, decay: float, skip: Optional[torch.Tensor] = None) -> None:
+    """``e.copy_(e * decay + (1. - decay) * m)`` for every pair, in ONE launch of smoe_ema_update_multi, bit-equal to torch's line:
+    f32 device tensors of equal shapes, contiguous, 16-byte aligned (ModelEma.update checks that and routes other entries to torch).
+    ``skip``: optional device f32 flag, non-zero = nothing is written.  Moves the version counters of ``emas``."""
+    pairs = list(zip(emas, models))
+    if not pairs:
+        return
+    if not all(_ema_kernel_ok(e, m) for e, m in pairs) or len({e.device for e, _ in pairs}) != 1:
+        raise ValueError("ema_update_: f32 contiguous 16-byte aligned tensor pairs of equal shapes on one GPU expected")
+    _ema_launch(_ema_table(pairs, pairs[0][0].device), len(pairs), decay, skip)
+    _bump_versions([e for e, _ in pairs])
