@@ -20,7 +20,8 @@ __device__ __forceinline__ float gelu_fwd(float v) {
   p = fmaf(p, t, 0.254829592f);
   p *= t;
   const float ex = __builtin_amdgcn_exp2f(z * z * -1.4426950408889634f);
-  return 0.5f * fmaf(a, fmaf(-p, ex, 1.0f), v);
+  // halves first: a + v overflows for v > 1.7e38 (gelu(3e38) came out inf); the same bits otherwise (a scaling by 0.5 is exact)
+  return fmaf(0.5f * a, fmaf(-p, ex, 1.0f), 0.5f * v);
 }
 
 template <typename T>

@@ -36,7 +36,8 @@ __device__ __forceinline__ float gelu_erf(float v) {
   p *= t;
   const float ex = __builtin_amdgcn_exp2f(z * z * -1.4426950408889634f);
   const float erf_abs = fmaf(-p, ex, 1.0f);
-  return 0.5f * fmaf(a, erf_abs, v);
+  // halves first: a + v overflows for v > 1.7e38 (gelu(3e38) came out inf); the same bits otherwise (a scaling by 0.5 is exact)
+  return fmaf(0.5f * a, erf_abs, 0.5f * v);
 }
 
 // GELU for the 16-bit-operand kernels: v * sigmoid(2 u(v)),  u(v) = v (c0 + c1 v^2 + c2 v^4 + c3 v^6 + c4 v^8) fitted to
