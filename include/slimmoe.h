@@ -176,10 +176,14 @@ int smoe_layernorm(const void* x, int x_dtype, const float* gamma, const float* 
 int smoe_attention_supported(int N, int head_dim);
 int smoe_attention_fwd(const void* qkv, void* out, int dtype, int B, int N, int H, int head_dim, float scale,
                        float* lse, void* stream);
-/* lse (may be NULL; N <= 256): [B, H, N] f32, log2 of the softmax normaliser in the scaled-score domain, p = exp2(s scale
+/* lse (may be NULL): [B, H, N] f32, log2 of the softmax normaliser in the scaled-score domain, p = exp2(s scale
  * log2(e) - lse) -- what the backward recomputes the probabilities from.
  * smoe_attention_bwd: dqkv [B,N,3,H,64] (same fused layout) from qkv, the forward's out and lse, and dout [B,N,H*64]:
- * dV = P^T dO, dS = P (dO V^T - rowsum(dO O)) scale, dQ = dS K, dK = dS^T Q; scores recomputed per (image, head), N <= 256. */
+ * dV = P^T dO, dS = P (dO V^T - rowsum(dO O)) scale, dQ = dS K, dK = dS^T Q; scores recomputed per (image, head).  N <= 640
+ * (smoe_attention_bwd_supported): one kernel with Q, K, V, dO whole in LDS for N <= 256; above that -- ViT-L/16 @384, N = 577,
+ * models/vision_transformer.py:1227-1236 -- a dQ kernel (K / V in LDS, keys walked in chunks) and a dK / dV kernel (one
+ * workgroup per 128-key block, Q / dO streamed) on the same stream, each finishing its outputs alone: no atomics, no
+ * workspace, the same bits on every call.                                                                            */
 int smoe_attention_bwd_supported(int N, int head_dim);
 int smoe_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int B, int N,
                        int H, int head_dim, float scale, void* stream);

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(ATT_THREADS, 3) void attn_fwd_kernel(const HT* __re
 constexpr int ATTL_THREADS = 512;
 template <typename HT, int NKT, int CH>
 __global__ __launch_bounds__(ATTL_THREADS, 2) void attn_fwd_long_kernel(const HT* __restrict__ qkv, HT* __restrict__ out, int N,
-                                                                        int H, float scale_log2e) {
+                                                                        int H, float scale_log2e, float* __restrict__ lse) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(CH % 2 == 0, "chunks are whole 32-key k-steps");
   constexpr int NCHUNK = (NKT + CH - 1) / CH;
@@ -387,6 +387,8 @@ __global__ __launch_bounds__(ATTL_THREADS, 2) void attn_fwd_long_kernel(const HT
       }
     }
     const float inv_l = 1.0f / lacc[0];
+    // training: the same log2 normaliser the short kernel stores (running maximum + log2 of the running denominator)
+    if (lse && g == 0 && q0 + qi < N) lse[((int64_t)b * H + h) * N + q0 + qi] = fmaf(m_run, scale_log2e, __log2f(lacc[0]));
     if (q0 + qi < N) {
       HT* op = out + ((int64_t)b * N + q0 + qi) * (H * ATT_D) + h * ATT_D + g * 4;
 #pragma unroll
@@ -408,12 +410,12 @@ __global__ __launch_bounds__(ATTL_THREADS, 2) void attn_fwd_long_kernel(const HT
 }
 
 template <typename HT, int NKT>
-int launch_attn_long(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t s) {
+int launch_attn_long(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t s, float* lse) {
   constexpr int CH = 10;
   const size_t smem = 2 * (size_t)NKT * 16 * 128;
   SMOE_ENSURE_SMEM(attn_fwd_long_kernel<HT, NKT, CH>);
   hipLaunchKernelGGL((attn_fwd_long_kernel<HT, NKT, CH>), dim3(B * H), dim3(ATTL_THREADS), smem, s, (const HT*)qkv, (HT*)out,
-                     N, H, scale * 1.4426950408889634f);
+                     N, H, scale * 1.4426950408889634f, lse);
   SMOE_CHECK_LAUNCH("smoe_attention_fwd/long");
   return 0;
 }
@@ -432,10 +434,6 @@ int launch_attn(const void* qkv, void* out, int B, int N, int H, float scale, hi
 template <typename HT>
 int attn_dispatch(const void* qkv, void* out, int B, int N, int H, float scale, hipStream_t s, float* lse) {
   const int nkt = (N + 15) / 16;
-  if (lse && nkt > 16) {
-    smoe_set_error("smoe_attention_fwd: the log-sum-exp output (training) is kept for N <= 256 only, N=%d", N);
-    return 1;
-  }
   if (nkt == 13) return launch_attn<HT, 13, true>(qkv, out, B, N, H, scale, s, lse);   // N = 197 / 198 (ViT @224 + cls)
   if (nkt == 4) return launch_attn<HT, 4, true>(qkv, out, B, N, H, scale, s, lse);
   if (nkt == 8) return launch_attn<HT, 8, true>(qkv, out, B, N, H, scale, s, lse);
@@ -445,10 +443,10 @@ int attn_dispatch(const void* qkv, void* out, int B, int N, int H, float scale, 
   if (nkt < 13) return launch_attn<HT, 13, false>(qkv, out, B, N, H, scale, s, lse);
   if (nkt < 16) return launch_attn<HT, 16, false>(qkv, out, B, N, H, scale, s, lse);
   // long sequences: K / V tiles held in LDS rounded up to the next instantiated size (rows >= N duplicate row N - 1)
-  if (nkt <= 20) return launch_attn_long<HT, 20>(qkv, out, B, N, H, scale, s);
-  if (nkt <= 30) return launch_attn_long<HT, 30>(qkv, out, B, N, H, scale, s);
-  if (nkt <= 37) return launch_attn_long<HT, 37>(qkv, out, B, N, H, scale, s);   // N = 577: ViT-L/16 @384 + cls
-  if (nkt <= 40) return launch_attn_long<HT, 40>(qkv, out, B, N, H, scale, s);
+  if (nkt <= 20) return launch_attn_long<HT, 20>(qkv, out, B, N, H, scale, s, lse);
+  if (nkt <= 30) return launch_attn_long<HT, 30>(qkv, out, B, N, H, scale, s, lse);
+  if (nkt <= 37) return launch_attn_long<HT, 37>(qkv, out, B, N, H, scale, s, lse);   // N = 577: ViT-L/16 @384 + cls
+  if (nkt <= 40) return launch_attn_long<HT, 40>(qkv, out, B, N, H, scale, s, lse);
   smoe_set_error("smoe_attention_fwd: N=%d unsupported (N <= 640)", N);
   return 1;
 }

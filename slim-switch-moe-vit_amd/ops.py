@@ -273,7 +273,8 @@ def attention_bwd_supported(N: int, head_dim: int) -> bool:
 
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, B: int, N: int, H: int,
                   head_dim: int, scale: float) -> torch.Tensor:
-    """dqkv (qkv's shape and dtype) of softmax(q k^T scale) v from the forward's ``out`` and ``lse``."""
+    """dqkv (qkv's shape and dtype) of softmax(q k^T scale) v from the forward's ``out`` and ``lse``; N <= 640 (one kernel up to
+    N = 256, a dQ and a dK / dV kernel above; no workspace either way)."""
     _chk(qkv, "qkv")
     _chk(out, "out", qkv.dtype)
     _chk(dout, "dout", qkv.dtype)

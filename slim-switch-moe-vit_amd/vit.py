@@ -348,7 +348,7 @@ class Attention(nn.Module):
             x2 = x2.contiguous()
         if not (dense.linear_supported(x2, self.qkv.weight) and dense.linear_supported(x2, self.proj.weight)
                 and ops.attention_supported(N, hd) and ops.attention_bwd_supported(N, hd) and DENSE_GEMM == "own"):
-            _warn_fallback("attention (training)", "shape outside the backward kernels' reach (N <= 256, head dim 64, C % 64 == 0)",
+            _warn_fallback("attention (training)", "shape outside the backward kernels' reach (N <= 640, head dim 64, C % 64 == 0)",
                            (B, N, C, self.num_heads))
             return None
         hc = _half_cache(self)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What the N > 256 fallback costs: torch's scaled_dot_product_attention forward + backward against the library's attention
-forward / backward kernels (N <= 256 only for the backward) at the training shapes.
+"""torch's scaled_dot_product_attention forward + backward (what training fell back to above N = 256 before the long backward
+kernels) against the library's attention forward-with-lse / backward kernels (N <= 640) at the training shapes.
 
     python tools/attn_bwd_probe.py        prints one line per (B, N, H) x implementation: forward us, backward us, TFLOP/s"""
 import os
@@ -51,7 +51,7 @@ def main():
         print(f"B {B:4d} N {N:4d} H {H:3d}  torch sdpa   fwd {tf:8.1f} us ({f_flop / tf * 1e-6:6.1f} TF)   bwd {tb:8.1f} us ({b_flop / tb * 1e-6:6.1f} TF)",
               flush=True)
         flat = qkv.reshape(B * N, 3 * H * hd)
-        own_bwd = ops.attention_bwd_supported(N, hd)          # (the forward keeps its log-sum-exp output for those N only)
+        own_bwd = ops.attention_bwd_supported(N, hd)
         if own_bwd:
             out, lse = ops.attention(flat, B, N, H, hd, scale, want_lse=True)
         of = timed(lambda: ops.attention(flat, B, N, H, hd, scale, want_lse=own_bwd))

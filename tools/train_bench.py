@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """BASELINE cfg 5 timing: forward + backward (+ AdamW step through NativeScaler) with the SwitchGate, capacity_factor 1.0 and the
 aux loss, (a) for ONE MoE layer at ViT-B dims (T = images x 197 rows) and (b) for the whole ViT-B/16 E=8 model.
-usage: train_bench.py [layer|model] [images] [iters] [model name]     (run under rocprofv3 --kernel-trace --stats for the per-kernel table)
+usage: train_bench.py [layer|model] [images] [iters] [model name] [image size]     (run under rocprofv3 --kernel-trace --stats for the per-kernel table)
 model name: default moe_base_patch16_224_expert8_top1 with the SwitchGate (cfg 5); a resmoe_* name = the reference's live block
 (token-skip gates, residual on the normed activations, naive gate; thresholds set so that ~40 % of the tokens skip).
 TRAIN_BENCH_EP=static|counted (model mode): the step through the EXPERT-PARALLEL code path on a one-rank RCCL group -- cfg 5's capacity
-gate on the static exchange (fixed slots, counts in-band, no host round trip) or on the counted one (a count read-back per layer)."""
-import os, sys, time, torch
+gate on the static exchange (fixed slots, counts in-band, no host round trip) or on the counted one (a count read-back per layer).
+image size: the fifth argument, else the `_<size>_` / `_<size>` field of the model name (moe_large_patch16_384_* -> 384), else 224."""
+import os, re, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import slim_switch_moe_vit_amd as sm
@@ -66,6 +67,8 @@ if what == "layer":
           f"{t_fb:.3f} ms  ({3 * fl / (t_fb * 1e-3) / 1e12:.0f} TFLOP/s over the 3 x 4Tdh expert-GEMM FLOPs)", flush=True)
 else:
     name = sys.argv[4] if len(sys.argv) > 4 else "moe_base_patch16_224_expert8_top1"
+    m_size = re.search(r"patch\d+_(\d+)(?:_|$)", name)
+    size = int(sys.argv[5]) if len(sys.argv) > 5 else (int(m_size.group(1)) if m_size else 224)
     if name.startswith("resmoe"):
         model = sm.create_model(name, num_classes=1000, drop_path_rate=0.1, starting_threshold=0.55, target_threshold=0.5)
         with torch.no_grad():
@@ -88,14 +91,15 @@ else:
         for m in model.modules():
             if isinstance(m, sm.FMoETransformerMLP):
                 m.force_ep = True
-        ep.set_static_tokens(model, images * 197, 197)
+        ntok = (size // 16) ** 2 + 1
+        ep.set_static_tokens(model, images * ntok, ntok)
         if ep_mode == "static":
             speculative = ep.set_speculative(model, 1.25, train=True) > 0
     model.train()
     opt = smo.AdamW(model.parameters(), lr=1e-4, weight_decay=0.05)
     scaler = smo.NativeScaler()
     crit = torch.nn.CrossEntropyLoss()
-    x = torch.randn(images, 3, 224, 224, generator=g).to(dev)
+    x = torch.randn(images, 3, size, size, generator=g).to(dev)
     y = torch.randint(0, 1000, (images,), generator=g).to(dev)
     moes = [m for m in model.modules() if isinstance(m, sm.FMoETransformerMLP)]
 
