@@ -506,6 +506,43 @@ int smoe_step_advance(float* step, const float* found_inf, void* stream);
 int smoe_ema_update_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, float decay,
                           float one_minus_decay, const float* skip, void* stream);
 
+/* ---- the recipe around the model (engine.py:46-47, 54; main.py:505-517 timm.data.Mixup, main.py:653-661 timm.loss.
+ * SoftTargetCrossEntropy / LabelSmoothingCrossEntropy; the reference's default run is --mixup 0.8 --cutmix 1.0 --smoothing 0.1).
+ * smoe_mixup_images : Mixup / CutMix IN PLACE on x f32 [B, C, H, W] (contiguous, B even, C*H*W < 2^31).  Sample b is paired with
+ *                     j = B-1-b.  Per sample: lam[b], one_minus[b] (f32, rounded by the caller) and box[b] = (yl, yh, xl, xh) i32.
+ *                     An empty box (yh <= yl or xh <= xl) = Mixup: out_b = (x_b * lam[b]) + (x_j * one_minus[b]), three separately
+ *                     rounded f32 operations, bit-equal to torch's `x.mul_(lam).add_(x.flip(0).mul_(1 - lam))`.  A non-empty box =
+ *                     CutMix: out_b = x_j inside the box, x_b outside.  lam[b] == 1: the sample is left untouched (nothing of its
+ *                     partner leaks in, not even 0 * inf).  Both samples of a pair are computed from the two ORIGINALS, so any mix
+ *                     of kinds, factors and boxes inside a pair is right in place (timm's batch, pair and elem modes).  One read and
+ *                     one write per element; a pair without a Mixup sample touches only the positions inside its boxes.  16-byte
+ *                     accesses when C*H*W % 4 == 0 and x is 16-byte aligned, element-wise otherwise.
+ * smoe_mixup_target : out f32 [B, num_classes] = (y1 * lam[b]) + (y2 * one_minus[b]), y1 = one_hot(labels[b]), y2 =
+ *                     one_hot(labels[B-1-b]) with values on / off (timm's mixup_target: off = smoothing / num_classes, on = 1 -
+ *                     smoothing + off), same three roundings.  labels i64 [B].  A label outside [0, num_classes) contributes `off`
+ *                     everywhere (no class is "on"); nothing is read back to check it.  One launch.
+ * smoe_soft_ce_fwd  : logits [B, C] (f32 / f16 / bf16, computed in f32) with the target of a row in ONE of two forms -- target f32
+ *                     [B, C] (labels NULL): row loss = sum(-t log_softmax(x)) = lse sum(t) - dot(t, x); or labels i64 [B] (target
+ *                     NULL) + smoothing: t = smoothing / C + (1 - smoothing) [c == label], sum(t) = 1 (smoothing 0 = cross-entropy;
+ *                     a label outside [0, C) puts the (1 - smoothing) nowhere).  Writes f32 [B] each: row_loss, row_max, row_logsum
+ *                     (lse = max + log(sum of exp(x - max)), kept as its two terms) and row_tsum, and *loss = mean of row_loss, summed
+ *                     in a fixed order: the same bits run to run.  Each logit and target is read once (online max / sum).  Two
+ *                     launches.  row_logsum is NaN whenever the log-sum-exp is not finite (a +inf or NaN logit, a row of -inf): that
+ *                     row's loss and whole gradient are then NaN, as torch's log_softmax makes them.
+ * smoe_soft_ce_bwd  : dlogits [B, C] (the logits' dtype, rounded once from f32) = *g (exp(x - max - logsum) sum(t) - t) / B; g is a DEVICE f32
+ *                     scalar (the gradient of the mean loss: it carries the loss scale).  Rows are independent.  B <= 65535.  One launch.
+ *                     Which non-finite value appears (inf or NaN) is not preserved: a -inf logit under a positive target gives a
+ *                     NaN row loss where exact arithmetic gives +inf.
+ * C <= 2^30.  B == 0 returns 0 at once; no allocation, no synchronisation, no atomics: all four can be captured.                             */
+int smoe_mixup_images(float* x, int64_t B, int C, int H, int W, const float* lam, const float* one_minus, const int32_t* box,
+                      void* stream);
+int smoe_mixup_target(const int64_t* labels, const float* lam, const float* one_minus, float on, float off, int64_t B,
+                      int num_classes, float* out, void* stream);
+int smoe_soft_ce_fwd(const void* logits, int dtype, const float* target, const int64_t* labels, float smoothing, int64_t B, int C,
+                     float* row_loss, float* row_max, float* row_logsum, float* row_tsum, float* loss, void* stream);
+int smoe_soft_ce_bwd(const void* logits, int dtype, const float* target, const int64_t* labels, float smoothing, int64_t B, int C,
+                     const float* row_max, const float* row_logsum, const float* row_tsum, const float* g, void* dlogits, void* stream);
+
 /* ---- small helpers ------------------------------------------------------------------------------------
  * elementwise cast between dtypes (weight shadow copies; not on the per-step path)                  */
 int smoe_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);

@@ -8,5 +8,7 @@ from .vit import (Block, VisionTransformer, create_model, register_model, list_m
 from .resmoe import *  # noqa: F401,F403
 from .engine import evaluate, accuracy, train_one_epoch, GraphedForward, GraphedTrainStep  # noqa: F401
 from .optim import AdamW, ModelEma, NativeScaler, invalidate_weight_images  # noqa: F401
+from .mixup import Mixup  # noqa: F401
+from .loss import SoftTargetCrossEntropy, LabelSmoothingCrossEntropy  # noqa: F401
 
 __version__ = "0.1.0"

@@ -104,6 +104,12 @@ SIGNATURES = {
     "smoe_amp_update": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_int, c_void_p]),
     "smoe_step_advance": (c_int, [c_void_p, c_void_p, c_void_p]),
     "smoe_ema_update_multi": (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
+    "smoe_mixup_images": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "smoe_mixup_target": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p]),
+    "smoe_soft_ce_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "smoe_soft_ce_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
     "smoe_unique_id_bytes": (c_int, []),
     "smoe_unique_id": (c_int, [c_void_p]),
     "smoe_ctx_create": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
@@ -133,7 +139,7 @@ _lib = None
 
 # what csrc/Makefile hashes into smoe_build_id(): the same names, sorted as strings, relative to csrc/
 _HASHED = ["api.hip", "router.hip", "router16.hip", "gate.hip", "dispatch.hip", "gemm.hip", "backward.hip", "attention.hip",
-           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "smoe_common.h", "router16_kernel.h", "router_mt_kernel.h", "gemm_persistent.h",
+           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "smoe_common.h", "router16_kernel.h", "router_mt_kernel.h", "gemm_persistent.h",
            "../../include/slimmoe.h", "Makefile"]
 
 

@@ -1,0 +1,393 @@
+// The recipe around the model in the reference's training step (engine.py:46-47, 54: `samples, targets = mixup_fn(samples, targets)`,
+// `loss = criterion(samples, outputs, targets)`; main.py:505-517 timm.data.Mixup, main.py:653-661 timm.loss.SoftTargetCrossEntropy /
+// LabelSmoothingCrossEntropy; the default run is --mixup 0.8 --cutmix 1.0 --smoothing 0.1):
+//   smoe_mixup_images : Mixup / CutMix of a batch IN PLACE, one read and one write of every image (upstream: a flipped copy and three
+//                       in-place passes), bit-equal to timm's lines in all three of its modes
+//   smoe_mixup_target : the mixed, smoothed one-hot targets in one launch (upstream: eight)
+//   smoe_soft_ce_fwd  : mean over rows of sum(-t * log_softmax(x)) for dense targets, or of the label-smoothing loss for integer
+//                       labels; one online max / sum pass per row + a fixed-order sum of the row losses (deterministic)
+//   smoe_soft_ce_bwd  : dlogits = g (softmax(x) sum(t) - t) / B in the logits' dtype, g a device scalar (it carries the loss scale)
+#include "smoe_common.h"
+#include <type_traits>
+
+namespace {
+
+constexpr int LOSS_THREADS = 256;
+constexpr int MIX_UNROLL = 4;     // vectors (or single elements on the scalar path) per thread of the image kernel
+
+// ---- Mixup / CutMix of the images ------------------------------------------------------------------------------------------
+// what one sample of a pair does with its own value a and its partner's value c at a position (y, x)
+struct MixRule {
+  float lam, om;
+  int yl, yh, xl, xh;
+  bool same, cut;      // same: lam == 1, the sample is left as it is; cut: a non-empty box (CutMix), else Mixup
+  __device__ __forceinline__ bool inside(int y, int x) const { return y >= yl && y < yh && x >= xl && x < xh; }
+  __device__ __forceinline__ float apply(float a, float c, int y, int x) const {
+    if (same) return a;
+    if (cut) return inside(y, x) ? c : a;
+    return __fadd_rn(__fmul_rn(a, lam), __fmul_rn(c, om));     // three roundings, as torch's x * lam + x_flipped * (1 - lam)
+  }
+};
+
+__device__ __forceinline__ MixRule mix_rule(const float* lam, const float* om, const int32_t* box, int b) {
+  MixRule r;
+  r.lam = lam[b]; r.om = om[b];
+  r.yl = box[4 * b]; r.yh = box[4 * b + 1]; r.xl = box[4 * b + 2]; r.xh = box[4 * b + 3];
+  r.same = r.lam == 1.0f;
+  r.cut = r.yh > r.yl && r.xh > r.xl;
+  return r;
+}
+
+// One workgroup set per PAIR (b, B-1-b): a thread loads position p of both images, computes both outputs from the two originals
+// and stores both -- correct in place whatever the two samples of the pair do.  VEC = 4: 16 bytes per lane and image (n % 4 == 0 and
+// a 16-byte aligned base); VEC = 1: everything else.  A pair without a Mixup sample touches only the positions inside its boxes.
+template <int VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void mixup_images_kernel(float* __restrict__ x, int B, uint32_t n, int H, int W,
+                                                                     const float* __restrict__ lam, const float* __restrict__ om,
+                                                                     const int32_t* __restrict__ box) {
+  const int b = blockIdx.y, j = B - 1 - b;
+  const MixRule rb = mix_rule(lam, om, box, b), rj = mix_rule(lam, om, box, j);
+  if (rb.same && rj.same) return;
+  const bool sparse = (rb.same || rb.cut) && (rj.same || rj.cut);    // no full pass: only box positions change
+  const bool need_pos = rb.cut || rj.cut;
+  float* __restrict__ xb = x + (size_t)b * n;
+  float* __restrict__ xj = x + (size_t)j * n;
+  const uint32_t hw = (uint32_t)H * (uint32_t)W;
+  const uint32_t base = blockIdx.x * (uint32_t)(LOSS_THREADS * VEC * MIX_UNROLL) + threadIdx.x * VEC;
+  float a[MIX_UNROLL][VEC], c[MIX_UNROLL][VEC];
+  int py[MIX_UNROLL], px[MIX_UNROLL];
+  bool live[MIX_UNROLL];
+#pragma unroll
+  for (int u = 0; u < MIX_UNROLL; ++u) {
+    const uint32_t p = base + u * (uint32_t)(LOSS_THREADS * VEC);
+    live[u] = p < n;      // (VEC = 4: n % 4 == 0, so a live vector is whole)
+    py[u] = px[u] = 0;
+    if (live[u] && need_pos) {
+      const uint32_t rem = p % hw;
+      py[u] = (int)(rem / (uint32_t)W);
+      px[u] = (int)(rem - (uint32_t)py[u] * (uint32_t)W);
+    }
+    if (live[u] && sparse) {
+      // the VEC positions from (py, px) on lie in rows py and (when the vector crosses a row end) the following ones
+      bool any = false;
+      int y = py[u], xx = px[u];
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) {
+        any |= (rb.cut && !rb.same && rb.inside(y, xx)) || (rj.cut && !rj.same && rj.inside(y, xx));
+        if (++xx == W) { xx = 0; if (++y == H) y = 0; }
+      }
+      live[u] = any;
+    }
+    if (live[u]) {
+      if constexpr (VEC == 4) {
+        const f32x4 va = *reinterpret_cast<const f32x4*>(xb + p), vc = *reinterpret_cast<const f32x4*>(xj + p);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { a[u][q] = va[q]; c[u][q] = vc[q]; }
+      } else {
+        a[u][0] = xb[p]; c[u][0] = xj[p];
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < MIX_UNROLL; ++u) {
+    if (!live[u]) continue;
+    const uint32_t p = base + u * (uint32_t)(LOSS_THREADS * VEC);
+    float ob[VEC], oj[VEC];
+    int y = py[u], xx = px[u];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) {
+      ob[q] = rb.apply(a[u][q], c[u][q], y, xx);
+      oj[q] = rj.apply(c[u][q], a[u][q], y, xx);
+      if (++xx == W) { xx = 0; if (++y == H) y = 0; }
+    }
+    if constexpr (VEC == 4) {
+      f32x4 vb, vj;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { vb[q] = ob[q]; vj[q] = oj[q]; }
+      if (!rb.same) *reinterpret_cast<f32x4*>(xb + p) = vb;
+      if (!rj.same) *reinterpret_cast<f32x4*>(xj + p) = vj;
+    } else {
+      if (!rb.same) xb[p] = ob[0];
+      if (!rj.same) xj[p] = oj[0];
+    }
+  }
+}
+
+// out[b, c] = one_hot(labels[b])[c] * lam[b] + one_hot(labels[B-1-b])[c] * om[b], three roundings (timm's mixup_target)
+__global__ __launch_bounds__(LOSS_THREADS) void mixup_target_kernel(const int64_t* __restrict__ labels, const float* __restrict__ lam,
+                                                                    const float* __restrict__ om, float on, float off, int B, int C,
+                                                                    float* __restrict__ out) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t l1 = labels[b], l2 = labels[B - 1 - b];
+    const float la = lam[b], lo = om[b];
+    const int c = blockIdx.x * LOSS_THREADS + threadIdx.x;
+    if (c < C) out[(size_t)b * C + c] = __fadd_rn(__fmul_rn(c == l1 ? on : off, la), __fmul_rn(c == l2 ? on : off, lo));
+  }
+}
+
+// ---- soft-target / label-smoothing cross-entropy ---------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ float to_f32(T v) {
+  if constexpr (std::is_same<T, bf16_bits>::value) return bf16_to_f32(v);
+  else return (float)v;
+}
+template <typename T> __device__ __forceinline__ T from_f32(float v) {
+  if constexpr (std::is_same<T, bf16_bits>::value) return f32_to_bf16(v);
+  else return (T)v;
+}
+
+// running (max, sum of exp(x - max)) of a row.  The maximum is never NaN (comparisons drop it), a NaN logit lives on in the sum;
+// a -inf logit adds 0; +inf - +inf = NaN poisons the sum, as it does torch's log_softmax.
+struct MaxSum {
+  float m, s;
+  __device__ __forceinline__ void merge(float m2, float s2) {
+    const float mm = fmaxf(m, m2);
+    s = s * (m == mm ? 1.0f : expf(m - mm)) + s2 * (m2 == mm ? 1.0f : expf(m2 - mm));
+    m = mm;
+  }
+};
+
+constexpr int CE_K = 8;     // logits per thread and step
+
+// compensated (Kahan) sum: a row's targets are one or two values near 1 among thousands near smoothing / C, and the row loss multiplies
+// their sum by the log-sum-exp -- a plain running sum's rounding (up to C / 256 half-ulps of 1 per thread) would show there
+struct Kahan {
+  float s = 0.f, c = 0.f;
+  __device__ __forceinline__ void add(float v) {
+    const float y = v - c, t = s + y;
+    c = (t - s) - y;
+    s = t;
+  }
+};
+
+// K logits of a thread at once (one exp of the running sum per step instead of one per logit)
+__device__ __forceinline__ void ce_step(MaxSum& ms, const float (&v)[CE_K], const bool (&ok)[CE_K]) {
+  const float ninf = -__builtin_inff();
+  float vm = ninf;
+#pragma unroll
+  for (int q = 0; q < CE_K; ++q) vm = fmaxf(vm, ok[q] ? v[q] : ninf);
+  if (vm > ms.m) { ms.s *= expf(ms.m - vm); ms.m = vm; }      // (ms.m == -inf: s is 0 or NaN, and stays that)
+  float add = 0.f;
+#pragma unroll
+  for (int q = 0; q < CE_K; ++q) add += (!ok[q] || v[q] == ninf) ? 0.f : expf(v[q] - ms.m);
+  ms.s += add;
+}
+
+// One workgroup per row.  Dense form (target != NULL): row loss = lse * sum(t) - dot(t, x).  Label form: t = smoothing / C everywhere
+// + (1 - smoothing) at the label (timm LabelSmoothingCrossEntropy; smoothing 0 = cross-entropy), sum(t) = 1.  A label outside [0, C)
+// puts the (1 - smoothing) nowhere.  The backward gets the row's maximum and log(sum of exp(x - max)) apart: exp((x - max) - logsum) has
+// the error of the small second term only, exp(x - lse) that of lse's rounding.  logsum is stored as NaN whenever the log-sum-exp is not
+// finite: the backward then poisons the whole row, as the reference's log_softmax does.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void soft_ce_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ target,
+                                                                   const int64_t* __restrict__ labels, float smoothing, int C,
+                                                                   float* __restrict__ row_loss, float* __restrict__ row_max,
+                                                                   float* __restrict__ row_logsum, float* __restrict__ row_tsum) {
+  __shared__ float red[4][LOSS_THREADS / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const T* __restrict__ x = logits + (size_t)row * C;
+  const float* __restrict__ t = target ? target + (size_t)row * C : nullptr;
+  MaxSum ms{-__builtin_inff(), 0.f};
+  Kahan kdot, kts;              // label form: kdot = sum(x)
+  const int span = LOSS_THREADS * CE_K;
+  for (int c0 = 0; c0 < C; c0 += span) {
+    float v[CE_K], tv[CE_K];
+    bool ok[CE_K];
+    if constexpr (VEC) {     // C % 8 == 0 and aligned bases: 8 consecutive logits (and targets) per lane
+      const int c = c0 + tid * CE_K;
+      const bool in = c < C;
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q) { ok[q] = in; v[q] = 0.f; tv[q] = 0.f; }
+      if (in) {
+        load8(x + c, v);
+        if (t) load8(t + c, tv);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q) {
+        const int c = c0 + q * LOSS_THREADS + tid;
+        ok[q] = c < C;
+        v[q] = ok[q] ? to_f32<T>(x[c]) : 0.f;
+        tv[q] = (ok[q] && t) ? t[c] : 0.f;
+      }
+    }
+    ce_step(ms, v, ok);
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      if (!ok[q]) continue;
+      if (t) { kdot.add(__fmul_rn(tv[q], v[q])); kts.add(tv[q]); }
+      else kdot.add(v[q]);
+    }
+  }
+  float dot = kdot.s, ts = kts.s;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float m2 = __shfl_xor(ms.m, m, 64), s2 = __shfl_xor(ms.s, m, 64);
+    ms.merge(m2, s2);
+    dot += __shfl_xor(dot, m, 64);
+    ts += __shfl_xor(ts, m, 64);
+  }
+  if ((tid & 63) == 0) { red[0][tid >> 6] = ms.m; red[1][tid >> 6] = ms.s; red[2][tid >> 6] = dot; red[3][tid >> 6] = ts; }
+  __syncthreads();
+  if (tid == 0) {
+    MaxSum a{red[0][0], red[1][0]}, b{red[0][2], red[1][2]};
+    a.merge(red[0][1], red[1][1]);
+    b.merge(red[0][3], red[1][3]);
+    a.merge(b.m, b.s);
+    dot = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+    ts = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+    float ls = logf(a.s);
+    float lse = a.m + ls;
+    if (!(fabsf(lse) <= 3.4028234664e38f)) lse = ls = __builtin_nanf("");
+    if (!t) {
+      const float off = smoothing / (float)C, conf = 1.0f - smoothing;
+      const int64_t l = labels[row];
+      float d = (l >= 0 && l < C) ? conf * to_f32<T>(x[l]) : 0.f;
+      if (smoothing != 0.f) d = fmaf(off, dot, d);
+      dot = d;
+      ts = 1.0f;
+    }
+    row_loss[row] = lse * ts - dot;
+    row_max[row] = a.m;
+    row_logsum[row] = ls;
+    row_tsum[row] = ts;
+  }
+}
+
+// *loss = (sum of row_loss in a fixed order) / B: one workgroup, the same tree whatever ran before
+__global__ __launch_bounds__(LOSS_THREADS) void row_mean_kernel(const float* __restrict__ row_loss, int B, float* __restrict__ loss) {
+  __shared__ float red[LOSS_THREADS / 64];
+  float acc = 0.f;
+  for (int r = threadIdx.x; r < B; r += LOSS_THREADS) acc += row_loss[r];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *loss = ((red[0] + red[1]) + (red[2] + red[3])) / (float)B;
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void soft_ce_bwd_kernel(const T* __restrict__ logits, const float* __restrict__ target,
+                                                                   const int64_t* __restrict__ labels, float smoothing, int B, int C,
+                                                                   const float* __restrict__ row_max, const float* __restrict__ row_logsum,
+                                                                   const float* __restrict__ row_tsum, const float* __restrict__ g,
+                                                                   T* __restrict__ dlogits) {
+  const int row = blockIdx.y;
+  const size_t at = (size_t)row * C;
+  const float mx = row_max[row], ls = row_logsum[row], ts = row_tsum[row], scale = *g / (float)B;
+  const float off = smoothing / (float)C, conf = 1.0f - smoothing;
+  const int64_t label = target ? -1 : labels[row];
+  if constexpr (VEC) {
+    const int c = (blockIdx.x * LOSS_THREADS + threadIdx.x) * CE_K;
+    if (c >= C) return;
+    float v[CE_K], tv[CE_K], o[CE_K];
+    load8(logits + at + c, v);
+    if (target) load8(target + at + c, tv);
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      const float tq = target ? tv[q] : off + (c + q == label ? conf : 0.f);
+      o[q] = (expf((v[q] - mx) - ls) * ts - tq) * scale;
+    }
+    store8(dlogits + at + c, o);
+  } else {
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      const int c = blockIdx.x * (LOSS_THREADS * CE_K) + q * LOSS_THREADS + threadIdx.x;
+      if (c >= C) continue;
+      const float tq = target ? target[at + c] : off + (c == label ? conf : 0.f);
+      dlogits[at + c] = from_f32<T>((expf((to_f32<T>(logits[at + c]) - mx) - ls) * ts - tq) * scale);
+    }
+  }
+}
+
+template <typename T>
+void launch_ce_fwd(bool vec, int B, hipStream_t s, const void* logits, const float* target, const int64_t* labels, float smoothing, int C,
+                   float* row_loss, float* row_max, float* row_logsum, float* row_tsum) {
+  if (vec) hipLaunchKernelGGL((soft_ce_fwd_kernel<T, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum);
+  else hipLaunchKernelGGL((soft_ce_fwd_kernel<T, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum);
+}
+
+template <typename T>
+void launch_ce_bwd(bool vec, dim3 grid, hipStream_t s, const void* logits, const float* target, const int64_t* labels, float smoothing,
+                   int B, int C, const float* row_max, const float* row_logsum, const float* row_tsum, const float* g, void* dlogits) {
+  if (vec) hipLaunchKernelGGL((soft_ce_bwd_kernel<T, true>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, B, C, row_max, row_logsum, row_tsum, g, (T*)dlogits);
+  else hipLaunchKernelGGL((soft_ce_bwd_kernel<T, false>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, B, C, row_max, row_logsum, row_tsum, g, (T*)dlogits);
+}
+
+// 8 consecutive elements per lane need 16-byte aligned rows of every operand
+bool ce_vec_ok(const void* logits, const void* target, const void* dlogits, int C) {
+  return C % CE_K == 0 && (((uintptr_t)logits | (uintptr_t)target | (uintptr_t)dlogits) & 15) == 0;
+}
+
+constexpr int GRID_Y_MAX = 65535;
+
+}  // namespace
+
+extern "C" int smoe_mixup_images(float* x, int64_t B, int C, int H, int W, const float* lam, const float* one_minus,
+                                 const int32_t* box, void* stream) {
+  SMOE_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0, "smoe_mixup_images: bad arguments");
+  SMOE_REQUIRE(B % 2 == 0, "smoe_mixup_images: the batch size must be even (sample b is mixed with sample B-1-b)");
+  const int64_t n = (int64_t)C * H * W;
+  SMOE_REQUIRE(n < (1ll << 31) && B / 2 <= GRID_Y_MAX, "smoe_mixup_images: C*H*W < 2^31 and B <= 131070 expected");
+  if (B == 0) return 0;
+  SMOE_REQUIRE(x && lam && one_minus && box, "smoe_mixup_images: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (n % 4 == 0 && ((uintptr_t)x & 15) == 0) {
+    const unsigned gx = (unsigned)((n + LOSS_THREADS * 4 * MIX_UNROLL - 1) / (LOSS_THREADS * 4 * MIX_UNROLL));
+    hipLaunchKernelGGL(mixup_images_kernel<4>, dim3(gx, (unsigned)(B / 2)), dim3(LOSS_THREADS), 0, s, x, (int)B, (uint32_t)n, H, W, lam, one_minus, box);
+  } else {
+    const unsigned gx = (unsigned)((n + LOSS_THREADS * MIX_UNROLL - 1) / (LOSS_THREADS * MIX_UNROLL));
+    hipLaunchKernelGGL(mixup_images_kernel<1>, dim3(gx, (unsigned)(B / 2)), dim3(LOSS_THREADS), 0, s, x, (int)B, (uint32_t)n, H, W, lam, one_minus, box);
+  }
+  SMOE_CHECK_LAUNCH("smoe_mixup_images");
+  return 0;
+}
+
+extern "C" int smoe_mixup_target(const int64_t* labels, const float* lam, const float* one_minus, float on, float off, int64_t B,
+                                 int num_classes, float* out, void* stream) {
+  SMOE_REQUIRE(B >= 0 && B < (1ll << 31), "smoe_mixup_target: bad arguments");
+  SMOE_REQUIRE(num_classes > 0, "smoe_mixup_target: num_classes must be positive");
+  if (B == 0) return 0;
+  SMOE_REQUIRE(labels && lam && one_minus && out, "smoe_mixup_target: null pointer");
+  const dim3 grid((unsigned)((num_classes + LOSS_THREADS - 1) / LOSS_THREADS), (unsigned)(B < GRID_Y_MAX ? B : GRID_Y_MAX));
+  hipLaunchKernelGGL(mixup_target_kernel, grid, dim3(LOSS_THREADS), 0, (hipStream_t)stream, labels, lam, one_minus, on, off, (int)B,
+                     num_classes, out);
+  SMOE_CHECK_LAUNCH("smoe_mixup_target");
+  return 0;
+}
+
+extern "C" int smoe_soft_ce_fwd(const void* logits, int dtype, const float* target, const int64_t* labels, float smoothing, int64_t B,
+                                int C, float* row_loss, float* row_max, float* row_logsum, float* row_tsum, float* loss, void* stream) {
+  SMOE_REQUIRE(B >= 0 && B < (1ll << 31) && C > 0 && C <= (1 << 30) && smoe_dtype_ok(dtype), "smoe_soft_ce_fwd: bad arguments (0 < C <= 2^30)");
+  SMOE_REQUIRE((target != nullptr) != (labels != nullptr) || B == 0, "smoe_soft_ce_fwd: exactly one of target and labels expected (null pointer)");
+  if (B == 0) return 0;
+  SMOE_REQUIRE(logits && row_loss && row_max && row_logsum && row_tsum && loss, "smoe_soft_ce_fwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(logits, target, nullptr, C);
+  switch (dtype) {
+    case SMOE_F32: launch_ce_fwd<float>(vec, (int)B, s, logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum); break;
+    case SMOE_F16: launch_ce_fwd<f16>(vec, (int)B, s, logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum); break;
+    default: launch_ce_fwd<bf16_bits>(vec, (int)B, s, logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum); break;
+  }
+  SMOE_CHECK_LAUNCH("smoe_soft_ce_fwd");
+  hipLaunchKernelGGL(row_mean_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_loss, (int)B, loss);
+  SMOE_CHECK_LAUNCH("smoe_soft_ce_fwd (mean)");
+  return 0;
+}
+
+extern "C" int smoe_soft_ce_bwd(const void* logits, int dtype, const float* target, const int64_t* labels, float smoothing, int64_t B,
+                                int C, const float* row_max, const float* row_logsum, const float* row_tsum, const float* g, void* dlogits, void* stream) {
+  SMOE_REQUIRE(B >= 0 && B <= GRID_Y_MAX && C > 0 && C <= (1 << 30) && smoe_dtype_ok(dtype), "smoe_soft_ce_bwd: bad arguments (B <= 65535, 0 < C <= 2^30)");
+  SMOE_REQUIRE((target != nullptr) != (labels != nullptr) || B == 0, "smoe_soft_ce_bwd: exactly one of target and labels expected (null pointer)");
+  if (B == 0) return 0;
+  SMOE_REQUIRE(logits && row_max && row_logsum && row_tsum && g && dlogits, "smoe_soft_ce_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(logits, target, dlogits, C);
+  const dim3 grid((unsigned)((C + LOSS_THREADS * CE_K - 1) / (LOSS_THREADS * CE_K)), (unsigned)B);
+  switch (dtype) {
+    case SMOE_F32: launch_ce_bwd<float>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
+    case SMOE_F16: launch_ce_bwd<f16>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
+    default: launch_ce_bwd<bf16_bits>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
+  }
+  SMOE_CHECK_LAUNCH("smoe_soft_ce_bwd");
+  return 0;
+}

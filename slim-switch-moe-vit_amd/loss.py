@@ -1,0 +1,84 @@
+"""The reference's training criteria (main.py:653-661): ``timm.loss.SoftTargetCrossEntropy`` when Mixup / CutMix is on (targets are
+dense rows), ``timm.loss.LabelSmoothingCrossEntropy`` when it is off and ``--smoothing`` > 0; engine.py:54 calls them in every step.
+
+timm is not installed where this package is developed or run: the two modules restate timm 0.4.12's ``timm/loss/cross_entropy.py``
+from its documented behaviour.  Upstream each is a torch composition -- log-softmax, multiply, negate, two sums, and their backward:
+about ten small launches inside a step whose kernels are all small (profiles/r05_tiny_models.md).  Here CUDA logits go through ONE
+``torch.autograd.Function`` over ``smoe_soft_ce_fwd`` / ``smoe_soft_ce_bwd``: two launches forward, one backward, deterministic, no
+host sync, capturable (engine.GraphedTrainStep).  Under autocast the 16-bit logits are taken as they are (the kernels compute in
+f32); the loss is an f32 scalar.  Anything else (CPU tensors, other dtypes or layouts, targets that need a gradient) takes timm's
+torch lines.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+
+_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+class _SoftCrossEntropy(torch.autograd.Function):
+    """mean over rows of sum(-t log_softmax(x)); ``dense``: f32 [B, C] target rows, else i64 [B] labels + ``smoothing``."""
+
+    @staticmethod
+    def forward(ctx, logits, target, dense: bool, smoothing: float):
+        loss, rows = ops.soft_ce_fwd(logits, target if dense else None, None if dense else target, smoothing)
+        ctx.save_for_backward(logits, target, rows)
+        ctx.dense, ctx.smoothing = dense, smoothing
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, rows = ctx.saved_tensors
+        if g.dtype != torch.float32:
+            g = g.float()
+        dx = ops.soft_ce_bwd(logits, rows, g.contiguous(), target if ctx.dense else None, None if ctx.dense else target, ctx.smoothing)
+        return dx, None, None, None
+
+
+def _logits_ok(x: torch.Tensor) -> bool:
+    return (x.is_cuda and x.dtype in _DTYPES and x.dim() >= 1 and x.is_contiguous() and x.shape[-1] > 0 and x.data_ptr() % 4 == 0
+            and 0 < x.numel() // x.shape[-1] <= 65535)
+
+
+class SoftTargetCrossEntropy(nn.Module):
+    """``timm.loss.SoftTargetCrossEntropy``: ``forward(x, target) = mean(sum(-target * log_softmax(x, dim=-1), dim=-1))``."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if (_logits_ok(x) and target.shape == x.shape and target.device == x.device and target.is_floating_point()
+                and not target.requires_grad):
+            C = x.shape[-1]
+            t = target.detach().reshape(-1, C)
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 4:
+                t = t.float().contiguous()
+            return _SoftCrossEntropy.apply(x.reshape(-1, C), t, True, 0.0)
+        loss = torch.sum(-target * F.log_softmax(x, dim=-1), dim=-1)
+        return loss.mean()
+
+
+class LabelSmoothingCrossEntropy(nn.Module):
+    """``timm.loss.LabelSmoothingCrossEntropy(smoothing=0.1)``: ``(1 - smoothing) * nll + smoothing * mean(-log_softmax(x))`` per row,
+    averaged; ``smoothing=0`` is plain cross-entropy.  ``x`` [B, C], ``target`` integer labels [B]."""
+
+    def __init__(self, smoothing: float = 0.1):
+        super().__init__()
+        assert smoothing < 1.0
+        self.smoothing = smoothing
+        self.confidence = 1. - smoothing
+
+    def forward(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if (_logits_ok(x) and x.dim() == 2 and target.dim() == 1 and target.numel() == x.shape[0] and target.device == x.device
+                and not target.is_floating_point()):
+            return _SoftCrossEntropy.apply(x, target.to(torch.int64).contiguous(), False, float(self.smoothing))
+        logprobs = F.log_softmax(x, dim=-1)
+        nll_loss = -logprobs.gather(dim=-1, index=target.unsqueeze(1))
+        nll_loss = nll_loss.squeeze(1)
+        smooth_loss = -logprobs.mean(dim=-1)
+        loss = self.confidence * nll_loss + self.smoothing * smooth_loss
+        return loss.mean()

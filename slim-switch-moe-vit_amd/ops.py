@@ -1252,3 +1252,81 @@ def group_colsum(src: torch.Tensor, offsets: torch.Tensor, group_end: Optional[t
                                ws_bytes, _stream(src))
     _lib.check(rc, "smoe_group_colsum")
     return out
+
+
+# ------------------------------------------------------------------------------------------ Mixup / CutMix and the soft-target loss
+def mixup_images_(x: torch.Tensor, lam: torch.Tensor, one_minus: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
+    """Mixup / CutMix of ``x`` f32 [B, C, H, W] IN PLACE (smoe_mixup_images): sample b with sample B-1-b, ``lam`` / ``one_minus`` f32 [B],
+    ``box`` i32 [B, 4] = (yl, yh, xl, xh) per sample (empty = Mixup, non-empty = CutMix, lam == 1 = untouched).  B even."""
+    _chk(x, "x", torch.float32, 4, align=4)
+    B, C, H, W = x.shape
+    _chk(lam, "lam", torch.float32, 1, align=4)
+    _chk(one_minus, "one_minus", torch.float32, 1, align=4)
+    _chk(box, "box", torch.int32, 2, align=4)
+    if lam.numel() != B or one_minus.numel() != B or tuple(box.shape) != (B, 4):
+        raise RuntimeError("mixup_images_: lam / one_minus [B] and box [B, 4] expected")
+    rc = _lib.load().smoe_mixup_images(_ptr(x), B, C, H, W, _ptr(lam), _ptr(one_minus), _ptr(box), _stream(x))
+    _lib.check(rc, "smoe_mixup_images")
+    return x
+
+
+def mixup_target(labels: torch.Tensor, lam: torch.Tensor, one_minus: torch.Tensor, on: float, off: float, num_classes: int) -> torch.Tensor:
+    """f32 [B, num_classes] = one_hot(labels, on, off) * lam + one_hot(labels.flip(0), on, off) * one_minus (smoe_mixup_target)."""
+    _chk(labels, "labels", torch.int64, 1, align=8)
+    _chk(lam, "lam", torch.float32, 1, align=4)
+    _chk(one_minus, "one_minus", torch.float32, 1, align=4)
+    B = labels.numel()
+    if lam.numel() != B or one_minus.numel() != B:
+        raise RuntimeError("mixup_target: lam / one_minus [B] expected")
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=labels.device)
+    rc = _lib.load().smoe_mixup_target(_ptr(labels), _ptr(lam), _ptr(one_minus), float(on), float(off), B, int(num_classes), _ptr(out),
+                                       _stream(labels))
+    _lib.check(rc, "smoe_mixup_target")
+    return out
+
+
+def _soft_ce_args(logits, target, labels):
+    _chk(logits, "logits", ndim=2, align=2)
+    B, C = logits.shape
+    if (target is None) == (labels is None):
+        raise RuntimeError("soft_ce: exactly one of target (f32 [B, C]) and labels (i64 [B]) expected")
+    if target is not None:
+        _chk(target, "target", torch.float32, 2, align=4)
+        if tuple(target.shape) != (B, C) or target.device != logits.device:
+            raise RuntimeError("soft_ce: target must be f32 [B, C] on the logits' device")
+    else:
+        _chk(labels, "labels", torch.int64, 1, align=8)
+        if labels.numel() != B or labels.device != logits.device:
+            raise RuntimeError("soft_ce: labels must be i64 [B] on the logits' device")
+    return B, C
+
+
+def soft_ce_fwd(logits: torch.Tensor, target: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                smoothing: float = 0.0):
+    """Mean over rows of sum(-t log_softmax(x)) (dense ``target``) or of the label-smoothing loss (``labels`` + ``smoothing``):
+    (loss f32 [], rows f32 [4, B] = per-row loss, maximum, log of the sum of exp(x - max), target sum -- the last three are what
+    soft_ce_bwd needs)."""
+    B, C = _soft_ce_args(logits, target, labels)
+    rows = torch.empty((4, B), dtype=torch.float32, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    rc = _lib.load().smoe_soft_ce_fwd(_ptr(logits), dtype_code(logits.dtype), _ptr(target), _ptr(labels), float(smoothing), B, C,
+                                      _ptr(rows), rows.data_ptr() + 4 * B, rows.data_ptr() + 8 * B, rows.data_ptr() + 12 * B, _ptr(loss),
+                                      _stream(logits))
+    _lib.check(rc, "smoe_soft_ce_fwd")
+    return loss, rows
+
+
+def soft_ce_bwd(logits: torch.Tensor, rows: torch.Tensor, g: torch.Tensor, target: Optional[torch.Tensor] = None,
+                labels: Optional[torch.Tensor] = None, smoothing: float = 0.0) -> torch.Tensor:
+    """dlogits = g (softmax(x) sum(t) - t) / B in the logits' dtype; ``g``: device f32 scalar; ``rows``: soft_ce_fwd's."""
+    B, C = _soft_ce_args(logits, target, labels)
+    _chk(rows, "rows", torch.float32, 2, align=4)
+    _chk(g, "g", torch.float32, align=4)
+    if tuple(rows.shape) != (4, B) or g.numel() != 1 or g.device != logits.device:
+        raise RuntimeError("soft_ce_bwd: rows f32 [4, B] and a device f32 scalar g expected")
+    out = torch.empty_like(logits)
+    rc = _lib.load().smoe_soft_ce_bwd(_ptr(logits), dtype_code(logits.dtype), _ptr(target), _ptr(labels), float(smoothing), B, C,
+                                      rows.data_ptr() + 4 * B, rows.data_ptr() + 8 * B, rows.data_ptr() + 12 * B, _ptr(g), _ptr(out),
+                                      _stream(logits))
+    _lib.check(rc, "smoe_soft_ce_bwd")
+    return out
