@@ -299,18 +299,26 @@ int smoe_gather_combine_ln(const void* y, int y_dtype, const int64_t* inv_pos, c
  * m_rows_max without a row map); the persistent kernel then keeps flat addressing for f32 outputs instead of the
  * buffer-addressed epilogue (whose descriptors need the bound: out_rows * N * 4 < 2 GiB).
  * Requires K*sizeof(ab) % 128 == 0 and N % 8 == 0.
- * variant: 9 = production choice (the 4 below as a PERSISTENT kernel, one workgroup per CU walking tiles, with the
- * direct-store epilogue for plain 16-bit outputs; 14 = the same with the LDS-staged epilogue everywhere, A/B reference;
- * 10-13 force tile height / schedule); 4 = production choice (8-wave ping-pong kernel, LDS-DMA staging; picks the 256- or 320-row tile by the
- * number of workgroup rounds and, for K >= 2048, the deep prefetch schedule); 5 / 6 force the 320- / 256-row tile,
- * 7 / 8 the deep schedule on the 256- / 320-row tile; 1-3 earlier LDS-DMA structures and 0 the register-staged
- * kernel (the only one for f32 operands or K % 64 != 0; chosen automatically then) are kept as A/B references.
+ * variant: 4-14 are a table of kernel family x tile plan, every entry a 256-column tile on the 8-wave ping-pong structure with
+ * LDS-DMA staging:                                  auto   320-row   256-row   256-row deep   320-row deep
+ *   one workgroup per tile                            4       5         6           7              8
+ *   persistent (one workgroup per CU walks tiles)     9      10        11          12             13
+ * auto = the tile rule smoe_grouped_gemm_plan states; deep = the deep prefetch schedule.  9 = production choice: the persistent
+ * family stores plain 16-bit outputs from the registers and f32 outputs through buffer descriptors; 14 = 9 with the LDS-staged
+ * epilogue everywhere (A/B reference).  A persistent variant whose operands reach 4 GiB, or with more than 63 groups, runs the
+ * same plan in the one-workgroup-per-tile family.  1-3 earlier LDS-DMA structures and 0 the register-staged kernel (the only
+ * one for f32 operands or K % 64 != 0; chosen automatically then) are kept as A/B references.
  * All variants compute the same function.                                                              */
 int smoe_grouped_gemm(const void* A, const void* W, const float* bias, const int32_t* offsets,
                       const int32_t* group_expert, int G, int n_experts, int64_t m_rows_max, int K, int N,
                       int ab_dtype, int epilogue, const int64_t* row_map, const float* row_scale,
                       const void* residual, const int64_t* a_gather, int a_div,
                       void* out, int64_t out_rows, int out_dtype, int variant, const int32_t* group_end, void* stream);
+/* The tile rule of the auto variants (4, 9, 14) for `rows` rows in G groups on the current device, as the explicit persistent
+ * variant it resolves to (10-13), for callers that name the variant from host-side numbers of their own:
+ *   t(h) = (ceil(rows / h) + G / 2) * ceil(N / 256) expected tiles of h rows (G / 2 rounds down), cus = the device's CU count;
+ *   320-row tiles iff ceil(t(320) / cus) * 1.25 <= ceil(t(256) / cus) (ties go to the taller tile); deep schedule iff K >= 2048. */
+int smoe_grouped_gemm_plan(int64_t rows, int G, int K, int N);
 
 /* OPTIONAL -- only in a library built with `make FFN=-DSMOE_FFN_FUSED` (it measured slower than the two smoe_grouped_gemm launches in
  * every scheduler design, profiles/r04_fused_ffn.md, and left the default build in round 5; bit-identical to them).

@@ -149,14 +149,13 @@ class _GroupFFN(torch.autograd.Function):
         the static expert exchange.  Rows outside the ranges (padding, header rows) are neither read nor written by any kernel of
         the forward or the backward: Y / drows are garbage there, and nobody downstream reads them."""
         cd = rows.dtype
-        ex = mod.experts
-        w1c, w2c = ex.htoh4.weight_as(cd), ex.h4toh.weight_as(cd)
-        Hp, A = ops.grouped_gemm_gelu_keep(rows, w1c, b1.detach().float() if b1 is not None else None, offsets,
-                                           group_expert=group_expert, variant=mod.gemm_variant, group_end=group_end)
+        w1c, b1f, w2c, b2f = mod.expert_operands(cd)   # (w1, b1, w2, b2 are the same parameters, passed for autograd's graph)
+        Hp, A = ops.grouped_gemm_gelu_keep(rows, w1c, b1f, offsets, group_expert=group_expert, variant=mod.gemm_variant,
+                                           group_end=group_end)
         if drop_mask is not None:
             A = A * drop_mask
-        Y = ops.grouped_gemm(A, w2c, b2.detach().float() if b2 is not None else None, offsets, ops.EPI_NONE, cd,
-                             variant=mod.gemm_variant, group_expert=group_expert, group_end=group_end, rows_hint=rows_hint)
+        Y = ops.grouped_gemm(A, w2c, b2f, offsets, ops.EPI_NONE, cd, variant=mod.gemm_variant, group_expert=group_expert,
+                             group_end=group_end, rows_hint=rows_hint)
         ctx.mod = mod
         ctx.zero_groups = zero_groups
         ctx.rows_hint = rows_hint

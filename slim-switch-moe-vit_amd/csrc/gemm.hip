@@ -23,6 +23,24 @@ constexpr int GEMM_THREADS = 256;
 constexpr int STAGE_BYTES = (BM + BN) * BK_BYTES;  // 32 KiB
 constexpr int C_PAD = 16;                          // bytes
 
+// One grouped-GEMM call as smoe_grouped_gemm validated it; the launchers below read it and unpack it at their kernel launch.
+struct GemmArgs {
+  const void *A, *W;
+  const float* bias;
+  const int32_t *offsets, *group_expert, *group_end;
+  int G;
+  int64_t m_rows_max;
+  int K, N, epilogue;
+  const int64_t* row_map;
+  const float* row_scale;
+  const void* residual;
+  void* out;
+  int64_t out_rows;
+  const int64_t* a_gather;
+  int a_div;
+  hipStream_t stream;
+};
+
 // exact-erf GELU, erf by Abramowitz-Stegun 7.1.26 (|erf error| <= 1.5e-7): 0.5*(v + |v|*erf(|v|/sqrt2)).
 // ~14 VALU ops incl. one v_rcp_f32 and one v_exp_f32; absolute GELU error < 1e-6 for |v| < 10.
 __device__ __forceinline__ float gelu_erf(float v) {
@@ -385,11 +403,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void grouped_gemm_t128(
 }
 
 template <typename AB, typename OT>
-int launch_t128(const void* A, const void* W, const float* bias, const int32_t* offsets, const int32_t* group_expert,
-                int E, int64_t m_rows_max, int K, int N, int epilogue, const int64_t* row_map, const float* row_scale,
-                const void* residual, void* out, hipStream_t s) {
-  const int n_tiles_n = (N + BN - 1) / BN;
-  const int max_m_tiles = (int)((m_rows_max + BM - 1) / BM) + E;
+int launch_t128(const GemmArgs& g) {
+  const int n_tiles_n = (g.N + BN - 1) / BN;
+  const int max_m_tiles = (int)((g.m_rows_max + BM - 1) / BM) + g.G;
   const int group_m = 8;
   const int m_groups = (max_m_tiles + group_m - 1) / group_m;
   const int grid = m_groups * group_m * n_tiles_n;
@@ -399,8 +415,9 @@ int launch_t128(const void* A, const void* W, const float* bias, const int32_t* 
   if (ctile > smem) smem = ctile;
   auto kern = grouped_gemm_t128<AB, OT>;
   SMOE_ENSURE_SMEM(grouped_gemm_t128<AB, OT>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(GEMM_THREADS), smem, s, (const AB*)A, (const AB*)W, bias, offsets, group_expert,
-                     E, K, N, epilogue, row_map, row_scale, (const OT*)residual, (OT*)out, n_tiles_n, group_m);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(GEMM_THREADS), smem, g.stream, (const AB*)g.A, (const AB*)g.W, g.bias, g.offsets,
+                     g.group_expert, g.G, g.K, g.N, g.epilogue, g.row_map, g.row_scale, (const OT*)g.residual, (OT*)g.out,
+                     n_tiles_n, group_m);
   SMOE_CHECK_LAUNCH("smoe_grouped_gemm");
   return 0;
 }
@@ -573,18 +590,17 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void grouped_gemm_glds(
 }
 
 template <typename AB, typename OT, int TBM, int TBN, int WM, int WN, int MINW>
-int launch_glds(const void* A, const void* W, const float* bias, const int32_t* offsets, const int32_t* group_expert,
-                int E, int64_t m_rows_max, int K, int N, int epilogue, const int64_t* row_map, const float* row_scale,
-                const void* residual, void* out, int group_m, hipStream_t s) {
-  const int n_tiles_n = (N + TBN - 1) / TBN;
-  const int max_m_tiles = (int)((m_rows_max + TBM - 1) / TBM) + E;
+int launch_glds(const GemmArgs& g, int group_m) {
+  const int n_tiles_n = (g.N + TBN - 1) / TBN;
+  const int max_m_tiles = (int)((g.m_rows_max + TBM - 1) / TBM) + g.G;
   const int m_groups = (max_m_tiles + group_m - 1) / group_m;
   const int grid = m_groups * group_m * n_tiles_n;
   const size_t smem = 2 * (size_t)(TBM + TBN) * BK_BYTES;
   auto kern = grouped_gemm_glds<AB, OT, TBM, TBN, WM, WN, MINW>;
   SMOE_ENSURE_SMEM(grouped_gemm_glds<AB, OT, TBM, TBN, WM, WN, MINW>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), smem, s, (const AB*)A, (const AB*)W, bias, offsets, group_expert,
-                     E, K, N, epilogue, row_map, row_scale, (const OT*)residual, (OT*)out, n_tiles_n, group_m);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), smem, g.stream, (const AB*)g.A, (const AB*)g.W, g.bias, g.offsets,
+                     g.group_expert, g.G, g.K, g.N, g.epilogue, g.row_map, g.row_scale, (const OT*)g.residual, (OT*)g.out,
+                     n_tiles_n, group_m);
   SMOE_CHECK_LAUNCH("smoe_grouped_gemm");
   return 0;
 }
@@ -1197,20 +1213,18 @@ __global__ __launch_bounds__(512, 2) void grouped_gemm_pp256(
 }
 
 template <typename AB, typename OT, int ABL = 0, int AFR = 4>
-int launch_pp256(const void* A, const void* W, const float* bias, const int32_t* offsets, const int32_t* group_expert,
-                 int E, int64_t m_rows_max, int K, int N, int epilogue, const int64_t* row_map, const float* row_scale,
-                 const void* residual, void* out, int group_m, hipStream_t s, const int64_t* a_gather = nullptr,
-                 int a_div = 1) {
+int launch_pp256(const GemmArgs& g, int group_m) {
   constexpr int TBM = 64 * AFR, TBN = 256;
-  const int n_tiles_n = (N + TBN - 1) / TBN;
-  const int max_m_tiles = (int)((m_rows_max + TBM - 1) / TBM) + E;
+  const int n_tiles_n = (g.N + TBN - 1) / TBN;
+  const int max_m_tiles = (int)((g.m_rows_max + TBM - 1) / TBM) + g.G;
   const int m_groups = (max_m_tiles + group_m - 1) / group_m;
   const int grid = m_groups * group_m * n_tiles_n;
   const size_t smem = 2 * (size_t)(TBM + TBN) * BK_BYTES;
   auto kern = grouped_gemm_pp256<AB, OT, ABL, 0, AFR>;
   SMOE_ENSURE_SMEM(grouped_gemm_pp256<AB, OT, ABL, 0, AFR>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, (const AB*)A, (const AB*)W, bias, offsets, group_expert, E, K, N,
-                     epilogue, row_map, row_scale, (const OT*)residual, (OT*)out, n_tiles_n, group_m, 0, a_gather, a_div);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, g.stream, (const AB*)g.A, (const AB*)g.W, g.bias, g.offsets,
+                     g.group_expert, g.G, g.K, g.N, g.epilogue, g.row_map, g.row_scale, (const OT*)g.residual, (OT*)g.out,
+                     n_tiles_n, group_m, 0, g.a_gather, g.a_div);
   SMOE_CHECK_LAUNCH("smoe_grouped_gemm");
   return 0;
 }
@@ -1234,126 +1248,111 @@ int launch_wgrad(const void* PT, const void* QT, const int32_t* offsets_pad, int
 }
 
 // token-major weight gradient (MODE 2): P [n_rows, R1], Q [n_rows, R2] row-major, offsets = plain row ranges
+template <typename AB, int AFR>
+int launch_wgrad_rows_tile(const void* P, const void* Q, const int32_t* offsets, const int32_t* group_end, int E, int R1, int R2,
+                           const void* zero16, float* out, hipStream_t s) {
+  constexpr int TBM = 64 * AFR, TBN = 256;
+  const int tn = (R2 + TBN - 1) / TBN, tm = (R1 + TBM - 1) / TBM;
+  const size_t smem = 2 * (size_t)(TBM + TBN) * BK_BYTES;
+  auto kern = grouped_gemm_pp256<AB, float, 0, 2, AFR>;
+  SMOE_ENSURE_SMEM(grouped_gemm_pp256<AB, float, 0, 2, AFR>);
+  hipLaunchKernelGGL(kern, dim3(E * tm * tn), dim3(512), smem, s, (const AB*)P, (const AB*)Q, (const float*)nullptr, offsets,
+                     group_end, E, 0, R2, (int)SMOE_EPI_NONE, (const int64_t*)nullptr, (const float*)nullptr,
+                     (const float*)zero16, out, tn, tm, R1, (const int64_t*)nullptr, 1);
+  SMOE_CHECK_LAUNCH("smoe_grouped_wgrad_rows");
+  return 0;
+}
+
 template <typename AB>
 int launch_wgrad_rows(const void* P, const void* Q, const int32_t* offsets, const int32_t* group_end, int E, int R1, int R2,
                       const void* zero16, float* out, hipStream_t s) {
   // Tile height 256 or 320 output rows, whichever needs fewer cost-weighted rounds of workgroups: the static grid has E x
   // tm x tn equal tiles, e.g. ViT-B's dW1 [3072, 768] x 8 experts = 288 tiles of 256 rows (two rounds on 256 CUs, the
   // second one an eighth full) or 240 of 320 rows (one round).
-  constexpr int TBN = 256;
-  const int tn = (R2 + TBN - 1) / TBN, tm4 = (R1 + 255) / 256, tm5 = (R1 + 319) / 320;
+  const int tn = (R2 + 255) / 256, tm4 = (R1 + 255) / 256, tm5 = (R1 + 319) / 320;
   const int64_t cus = smoe_num_cus();
   const double c4 = (double)(((int64_t)E * tm4 * tn + cus - 1) / cus), c5 = 1.25 * (double)(((int64_t)E * tm5 * tn + cus - 1) / cus);
-  if (c5 < c4) {
-    const size_t smem = 2 * (size_t)(320 + TBN) * BK_BYTES;
-    auto kern = grouped_gemm_pp256<AB, float, 0, 2, 5>;
-    SMOE_ENSURE_SMEM(grouped_gemm_pp256<AB, float, 0, 2, 5>);
-    hipLaunchKernelGGL(kern, dim3(E * tm5 * tn), dim3(512), smem, s, (const AB*)P, (const AB*)Q, (const float*)nullptr, offsets,
-                       group_end, E, 0, R2, (int)SMOE_EPI_NONE, (const int64_t*)nullptr, (const float*)nullptr,
-                       (const float*)zero16, out, tn, tm5, R1, (const int64_t*)nullptr, 1);
-  } else {
-    const size_t smem = 2 * (size_t)(256 + TBN) * BK_BYTES;
-    auto kern = grouped_gemm_pp256<AB, float, 0, 2>;
-    SMOE_ENSURE_SMEM(grouped_gemm_pp256<AB, float, 0, 2>);
-    hipLaunchKernelGGL(kern, dim3(E * tm4 * tn), dim3(512), smem, s, (const AB*)P, (const AB*)Q, (const float*)nullptr, offsets,
-                       group_end, E, 0, R2, (int)SMOE_EPI_NONE, (const int64_t*)nullptr, (const float*)nullptr,
-                       (const float*)zero16, out, tn, tm4, R1, (const int64_t*)nullptr, 1);
-  }
-  SMOE_CHECK_LAUNCH("smoe_grouped_wgrad_rows");
-  return 0;
+  if (c5 < c4) return launch_wgrad_rows_tile<AB, 5>(P, Q, offsets, group_end, E, R1, R2, zero16, out, s);
+  return launch_wgrad_rows_tile<AB, 4>(P, Q, offsets, group_end, E, R1, R2, zero16, out, s);
+}
+
+// The tile rule of the 256-column kernels, stated once.  tall: 320- instead of 256-row tiles when they need no more cost-weighted
+// rounds of workgroups.  t = expected tile count (each group's last tile is half full on average; the kernel balances the real
+// ones), a 320-row tile costs 1.25 of a 256-row one, ties go to the taller tile (more FLOP per LDS-fill byte).  deep: the
+// half-organised LDS with two half-tiles in flight across the tile boundary: +3-4 % on long K loops (GEMM-2, 8192^3), -3 % at
+// K = 768 where the uneven per-wave DMA split of the 320-row tile shows.
+struct TilePlan { bool tall, deep; };
+TilePlan pick_tiles(int64_t rows, int G, int K, int N) {
+  const int ntn = (N + 255) / 256;
+  const int64_t t256 = ((rows + 255) / 256 + G / 2) * ntn, t320 = ((rows + 319) / 320 + G / 2) * ntn;
+  const int cus = smoe_num_cus();
+  return {(double)((t320 + cus - 1) / cus) * 1.25 <= (double)((t256 + cus - 1) / cus), K >= 2048};
+}
+
+// Variants 4-14 are a table, family x plan:        auto   320   256   256 deep   320 deep
+//   one workgroup per tile (launch_pp256)            4     5     6       7          8
+//   persistent             (launch_ps)               9    10    11      12         13       14 = 9 without the direct-store epilogues
+constexpr int PP_FIRST = 4, PS_FIRST = 9, PS_STAGED = 14;
+constexpr TilePlan FIXED_PLANS[5] = {{false, false} /* auto: pick_tiles */, {true, false}, {false, false}, {false, true}, {true, true}};
+struct VariantCode { bool persistent; int plan; bool allow_direct; };   // plan = column of the table above
+bool decode_variant(int variant, VariantCode& c) {
+  if (variant < PP_FIRST || variant > PS_STAGED) return false;
+  c.persistent = variant >= PS_FIRST;
+  c.allow_direct = variant != PS_STAGED;
+  c.plan = variant == PS_STAGED ? 0 : variant - (c.persistent ? PS_FIRST : PP_FIRST);
+  return true;
+}
+
+// the runtime {tall, deep} as the template arguments of each family
+template <typename AB, typename OT>
+int launch_pp256_plan(const GemmArgs& g, TilePlan p, int group_m) {
+  if (p.tall) return p.deep ? launch_pp256<AB, OT, 16, 5>(g, group_m) : launch_pp256<AB, OT, 0, 5>(g, group_m);
+  return p.deep ? launch_pp256<AB, OT, 16, 4>(g, group_m) : launch_pp256<AB, OT, 0, 4>(g, group_m);
+}
+template <typename AB, typename OT>
+int launch_ps_plan(const GemmArgs& g, TilePlan p, bool allow_direct) {
+  if (p.tall) return p.deep ? launch_ps<AB, OT, 5, true>(g, 4, allow_direct) : launch_ps<AB, OT, 5, false>(g, 4, allow_direct);
+  return p.deep ? launch_ps<AB, OT, 4, true>(g, 4, allow_direct) : launch_ps<AB, OT, 4, false>(g, 4, allow_direct);
 }
 
 template <typename AB, typename OT>
-int launch_variant(int variant, const void* A, const void* W, const float* bias, const int32_t* offsets,
-                   const int32_t* group_expert, int E, int64_t m_rows_max, int K, int N, int epilogue,
-                   const int64_t* row_map, const float* row_scale, const void* residual, void* out, hipStream_t s,
-                   const int64_t* a_gather, int a_div, const int32_t* group_end, int64_t out_rows) {
+int launch_variant(int variant, const GemmArgs& g) {
   if constexpr (sizeof(AB) == 2) {
     switch (variant) {
-      case 1: return launch_glds<AB, OT, 128, 128, 2, 2, 2>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 8, s);
-      case 2: return launch_glds<AB, OT, 256, 128, 2, 2, 1>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 3: return launch_glds<AB, OT, 256, 256, 2, 4, 2>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 4: {  // auto: 256- or 320-row tiles, whichever needs fewer (cost-weighted) rounds of workgroups
-        const int ntn = (N + 255) / 256;
-        // expected tile counts (each group's last tile is half full on average); the kernel balances the real ones
-        const int64_t t256 = ((m_rows_max + 255) / 256 + E / 2) * ntn, t320 = ((m_rows_max + 319) / 320 + E / 2) * ntn;
-        const int cus = smoe_num_cus();
-        const double c256 = (double)((t256 + cus - 1) / cus) * 1.0, c320 = (double)((t320 + cus - 1) / cus) * 1.25;
-        // deep = half-organised LDS with two half-tiles in flight across the tile boundary (variants 7 / 8): +3-4 % on
-        // long K loops (GEMM-2, 8192^3), -3 % at K = 768 where the uneven per-wave DMA split of the 320-row tile shows
-        const bool deep = K >= 2048;
-        if (c320 <= c256) {  // ties go to the taller tile (more FLOP per LDS-fill byte)
-          if (deep) return launch_pp256<AB, OT, 16, 5>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-          return launch_pp256<AB, OT, 0, 5>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-        }
-        if (deep) return launch_pp256<AB, OT, 16, 4>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-        return launch_pp256<AB, OT>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-      }
+      case 1: return launch_glds<AB, OT, 128, 128, 2, 2, 2>(g, 8);
+      case 2: return launch_glds<AB, OT, 256, 128, 2, 2, 1>(g, 4);
+      case 3: return launch_glds<AB, OT, 256, 256, 2, 4, 2>(g, 4);
 #ifdef SMOE_DIAG
-      case 5: {
-        const char* gm = getenv("SMOE_GROUP_M");
-        return launch_pp256<AB, OT, 0, 5>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, gm ? atoi(gm) : 4, s, a_gather, a_div);
-      }
-#else
-      case 5: return launch_pp256<AB, OT, 0, 5>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-#endif
-      case 9: {  // as 4 (auto tile height / schedule), on the persistent kernel
-        const int ntn = (N + 255) / 256;
-        const int64_t t256 = ((m_rows_max + 255) / 256 + E / 2) * ntn, t320 = ((m_rows_max + 319) / 320 + E / 2) * ntn;
-        const int cus = smoe_num_cus();
-        const double c256 = (double)((t256 + cus - 1) / cus) * 1.0, c320 = (double)((t320 + cus - 1) / cus) * 1.25;
-        const bool deep = K >= 2048;
-        if (c320 <= c256) {
-          if (deep) return launch_ps<AB, OT, 5, true>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-          return launch_ps<AB, OT, 5, false>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-        }
-        if (deep) return launch_ps<AB, OT, 4, true>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-        return launch_ps<AB, OT, 4, false>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-      }
-      case 14: {  // as 9 with the LDS-staged epilogue everywhere (A/B reference of the direct-store epilogue)
-        const int ntn = (N + 255) / 256;
-        const int64_t t256 = ((m_rows_max + 255) / 256 + E / 2) * ntn, t320 = ((m_rows_max + 319) / 320 + E / 2) * ntn;
-        const int cus = smoe_num_cus();
-        const double c256 = (double)((t256 + cus - 1) / cus) * 1.0, c320 = (double)((t320 + cus - 1) / cus) * 1.25;
-        const bool deep = K >= 2048;
-        if (c320 <= c256) {
-          if (deep) return launch_ps<AB, OT, 5, true>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows, false);
-          return launch_ps<AB, OT, 5, false>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows, false);
-        }
-        if (deep) return launch_ps<AB, OT, 4, true>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows, false);
-        return launch_ps<AB, OT, 4, false>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows, false);
-      }
-      case 10: return launch_ps<AB, OT, 5, false>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-      case 11: return launch_ps<AB, OT, 4, false>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-      case 12: return launch_ps<AB, OT, 4, true>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-      case 13: return launch_ps<AB, OT, 5, true>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div, group_end, out_rows);
-      case 6: return launch_pp256<AB, OT>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-      case 7: return launch_pp256<AB, OT, 16, 4>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-      case 8: return launch_pp256<AB, OT, 16, 5>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s, a_gather, a_div);
-#ifdef SMOE_DIAG
-      case 41: return launch_pp256<AB, OT, 1>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 42: return launch_pp256<AB, OT, 2>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 43: return launch_pp256<AB, OT, 3>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 44: return launch_pp256<AB, OT, 4>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 46: return launch_pp256<AB, OT, 6>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 48: return launch_pp256<AB, OT, 8>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
-      case 47: return launch_pp256<AB, OT, 7>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, 4, s);
+      case 41: return launch_pp256<AB, OT, 1>(g, 4);
+      case 42: return launch_pp256<AB, OT, 2>(g, 4);
+      case 43: return launch_pp256<AB, OT, 3>(g, 4);
+      case 44: return launch_pp256<AB, OT, 4>(g, 4);
+      case 46: return launch_pp256<AB, OT, 6>(g, 4);
+      case 48: return launch_pp256<AB, OT, 8>(g, 4);
+      case 47: return launch_pp256<AB, OT, 7>(g, 4);
 #endif
       default: break;
     }
+    VariantCode c;
+    if (decode_variant(variant, c)) {
+      const TilePlan p = c.plan ? FIXED_PLANS[c.plan] : pick_tiles(g.m_rows_max, g.G, g.K, g.N);
+      if (c.persistent) return launch_ps_plan<AB, OT>(g, p, c.allow_direct);
+      int group_m = 4;
+#ifdef SMOE_DIAG
+      if (const char* gm = variant == 5 ? getenv("SMOE_GROUP_M") : nullptr) group_m = atoi(gm);
+#endif
+      return launch_pp256_plan<AB, OT>(g, p, group_m);
+    }
   }
-  return launch_t128<AB, OT>(A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, s);
+  return launch_t128<AB, OT>(g);
 }
 
 template <typename AB>
-int dispatch_out(int variant, const void* A, const void* W, const float* bias, const int32_t* offsets, const int32_t* group_expert,
-                 int E, int64_t m_rows_max, int K, int N, int epilogue, const int64_t* row_map, const float* row_scale,
-                 const void* residual, void* out, int out_dtype, hipStream_t s, const int64_t* a_gather, int a_div,
-                 const int32_t* group_end, int64_t out_rows) {
+int dispatch_out(int variant, const GemmArgs& g, int out_dtype) {
   switch (out_dtype) {
-    case SMOE_F32: return launch_variant<AB, float>(variant, A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, s, a_gather, a_div, group_end, out_rows);
-    case SMOE_F16: return launch_variant<AB, f16>(variant, A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, s, a_gather, a_div, group_end, out_rows);
-    case SMOE_BF16: return launch_variant<AB, bf16_bits>(variant, A, W, bias, offsets, group_expert, E, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, s, a_gather, a_div, group_end, out_rows);
+    case SMOE_F32: return launch_variant<AB, float>(variant, g);
+    case SMOE_F16: return launch_variant<AB, f16>(variant, g);
+    case SMOE_BF16: return launch_variant<AB, bf16_bits>(variant, g);
   }
   smoe_set_error("smoe_grouped_gemm: bad out_dtype %d", out_dtype);
   return 1;
@@ -1411,24 +1410,39 @@ extern "C" int smoe_grouped_gemm(const void* A, const void* W, const float* bias
   if (m_rows_max == 0) return 0;
   SMOE_REQUIRE(A && W && out, "smoe_grouped_gemm: null pointer");
   if (K % 64 != 0 || smoe_dtype_size(ab_dtype) != 2) variant = 0;
-  SMOE_REQUIRE(!a_gather || (variant >= 4 && variant <= 14 && a_div >= 1),
+  SMOE_REQUIRE(!a_gather || (variant >= PP_FIRST && variant <= PS_STAGED && a_div >= 1),
                "smoe_grouped_gemm: a_gather needs variant 4-14 (16-bit operands, K %% 64 == 0)");
-  if (variant >= 9 && variant <= 14) {
-    // the persistent kernel addresses both operands with 32-bit byte offsets; operands of 4 GiB and more take the
-    // one-workgroup-per-tile kernel of the same tile height / schedule (9, 14 -> 4, 10 -> 5, 11 -> 6, 12 -> 7, 13 -> 8)
+  VariantCode code;
+  const bool tiled = decode_variant(variant, code);   // variants 4-14: family x plan
+  if (tiled && code.persistent) {
+    // the persistent kernel addresses both operands with 32-bit byte offsets and keeps its group table in 64 lanes: operands of
+    // 4 GiB and more, or more than 63 groups, take the same plan in the one-workgroup-per-tile family
     const uint64_t a_bytes = (uint64_t)m_rows_max * (uint64_t)K * 2u, w_bytes = (uint64_t)n_experts * (uint64_t)N * (uint64_t)K * 2u;
-    if (a_bytes >= (1ull << 32) || w_bytes >= (1ull << 32) || G > 63) variant = variant == 14 ? 4 : variant - 5;   // (its group table: 64 lanes)
+    if (a_bytes >= (1ull << 32) || w_bytes >= (1ull << 32) || G > 63) {
+      code.persistent = false;
+      variant = PP_FIRST + code.plan;
+    }
   }
-  SMOE_REQUIRE(!group_end || (variant >= 9 && variant <= 14),
+  SMOE_REQUIRE(!group_end || (tiled && code.persistent),
                "smoe_grouped_gemm: group_end (separate row ranges per group) needs the persistent kernel: variant 9-14, 16-bit "
                "operands under 4 GiB, K %% 64 == 0, at most 63 groups");
-  hipStream_t s = (hipStream_t)stream;
+  const GemmArgs g{A, W, bias, offsets, group_expert, group_end, G, m_rows_max, K, N, epilogue, row_map, row_scale, residual,
+                   out, out_rows, a_gather, a_div, (hipStream_t)stream};
   switch (ab_dtype) {
-    case SMOE_F32: return dispatch_out<float>(variant, A, W, bias, offsets, group_expert, G, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, out_dtype, s, a_gather, a_div, group_end, out_rows);
-    case SMOE_F16: return dispatch_out<f16>(variant, A, W, bias, offsets, group_expert, G, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, out_dtype, s, a_gather, a_div, group_end, out_rows);
-    case SMOE_BF16: return dispatch_out<bf16_bits>(variant, A, W, bias, offsets, group_expert, G, m_rows_max, K, N, epilogue, row_map, row_scale, residual, out, out_dtype, s, a_gather, a_div, group_end, out_rows);
+    case SMOE_F32: return dispatch_out<float>(variant, g, out_dtype);
+    case SMOE_F16: return dispatch_out<f16>(variant, g, out_dtype);
+    case SMOE_BF16: return dispatch_out<bf16_bits>(variant, g, out_dtype);
   }
   return 1;
+}
+
+// The explicit persistent variant (10-13) that the auto variants (4, 9, 14) resolve to for `rows` rows in G groups on the current
+// device: the library's tile rule for callers that must name the variant ahead of the call.
+extern "C" int smoe_grouped_gemm_plan(int64_t rows, int G, int K, int N) {
+  const TilePlan p = pick_tiles(rows, G, K, N);
+  for (int i = 1; i < 5; ++i)
+    if (FIXED_PLANS[i].tall == p.tall && FIXED_PLANS[i].deep == p.deep) return PS_FIRST + i;
+  return PS_FIRST;   // not reached: FIXED_PLANS[1..4] are the four {tall, deep} pairs
 }
 
 #ifdef SMOE_FFN_FUSED
@@ -1498,10 +1512,10 @@ extern "C" int smoe_grouped_gemm_gelu_keep(const void* A, const void* W, const f
   SMOE_REQUIRE(A && W && pre_out && out, "smoe_grouped_gemm_gelu_keep: null pointer");
   const uint64_t a_bytes = (uint64_t)m_rows_max * (uint64_t)K * 2u, w_bytes = (uint64_t)n_experts * (uint64_t)N * (uint64_t)K * 2u;
   if (K % 64 != 0 || G > 63 || a_bytes >= (1ull << 32) || w_bytes >= (1ull << 32)) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  if (ab_dtype == SMOE_F16)
-    return launch_ps<f16, f16, 5, false, true>(A, W, bias, offsets, group_expert, G, m_rows_max, K, N, SMOE_EPI_GELU, nullptr, nullptr, pre_out, out, 4, s, nullptr, 1, group_end, 0);
-  return launch_ps<bf16_bits, bf16_bits, 5, false, true>(A, W, bias, offsets, group_expert, G, m_rows_max, K, N, SMOE_EPI_GELU, nullptr, nullptr, pre_out, out, 4, s, nullptr, 1, group_end, 0);
+  const GemmArgs g{A, W, bias, offsets, group_expert, group_end, G, m_rows_max, K, N, SMOE_EPI_GELU, nullptr, nullptr,
+                   /*residual=*/pre_out, out, /*out_rows=*/0, /*a_gather=*/nullptr, 1, (hipStream_t)stream};
+  if (ab_dtype == SMOE_F16) return launch_ps<f16, f16, 5, false, true>(g, 4);
+  return launch_ps<bf16_bits, bf16_bits, 5, false, true>(g, 4);
 }
 
 // Weight gradients of a grouped linear (fmoe_cuda.linear_backward's grad_W):

@@ -1102,13 +1102,10 @@ __global__ __launch_bounds__(512, 2) void expert_ffn_fused(
 #endif  // SMOE_FFN_FUSED
 
 template <typename AB, typename OT, int AFR, bool DEEP, bool KEEP = false>
-int launch_ps(const void* A, const void* W, const float* bias, const int32_t* offsets, const int32_t* group_expert, int E,
-              int64_t m_rows_max, int K, int N, int epilogue, const int64_t* row_map, const float* row_scale,
-              const void* residual, void* out, int group_m, hipStream_t s, const int64_t* a_gather, int a_div,
-              const int32_t* group_end, int64_t out_rows, bool allow_direct = true) {
+int launch_ps(const GemmArgs& g, int group_m, bool allow_direct = true) {
   constexpr int TBM = 64 * AFR, TBN = 256;
-  const int n_tiles_n = (N + TBN - 1) / TBN;
-  const int64_t max_tiles = ((m_rows_max + TBM - 1) / TBM + E) * n_tiles_n;
+  const int n_tiles_n = (g.N + TBN - 1) / TBN;
+  const int64_t max_tiles = ((g.m_rows_max + TBM - 1) / TBM + g.G) * n_tiles_n;
   int grid = (smoe_num_cus() - smoe_reserved_cus()) & ~7;   // one workgroup per CU (the LDS is full); a multiple of 8 (XCD slots);
                                                             // minus the CUs left to other streams (smoe_set_reserved_cus)
   if (grid < 8) grid = 8;
@@ -1128,13 +1125,17 @@ int launch_ps(const void* A, const void* W, const float* bias, const int32_t* of
   if (n_block && n_tiles_n % n_block) n_block = 0;
 #endif
   if (n_block) group_m = -(group_m | (n_block << 8));
+  auto launch = [&](auto kern) {   // the three kernels below differ in their epilogue only and take the same arguments
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 160 * 1024, g.stream, (const AB*)g.A, (const AB*)g.W, g.bias, g.offsets,
+                       g.group_expert, g.G, g.K, g.N, g.epilogue, g.row_map, g.row_scale, (const OT*)g.residual, (OT*)g.out,
+                       n_tiles_n, group_m, g.a_gather, g.a_div, (int)g.m_rows_max, g.group_end);
+  };
   if constexpr (!KEEP && sizeof(OT) == 2) {
     // plain 16-bit outputs (GEMM-1, qkv, patch embedding): the epilogue that stores from the registers
-    if (allow_direct && !row_map && !residual && (epilogue == SMOE_EPI_NONE || epilogue == SMOE_EPI_GELU) && (int64_t)N * TBM * 2 < (1ll << 31)) {
+    if (allow_direct && !g.row_map && !g.residual && (g.epilogue == SMOE_EPI_NONE || g.epilogue == SMOE_EPI_GELU) &&
+        (int64_t)g.N * TBM * 2 < (1ll << 31)) {
       SMOE_ENSURE_SMEM(grouped_gemm_ps<AB, OT, AFR, DEEP, false, true>);
-      hipLaunchKernelGGL((grouped_gemm_ps<AB, OT, AFR, DEEP, false, true>), dim3(grid), dim3(512), 160 * 1024, s, (const AB*)A,
-                         (const AB*)W, bias, offsets, group_expert, E, K, N, epilogue, row_map, row_scale, (const OT*)residual,
-                         (OT*)out, n_tiles_n, group_m, a_gather, a_div, (int)m_rows_max, group_end);
+      launch(grouped_gemm_ps<AB, OT, AFR, DEEP, false, true>);
       SMOE_CHECK_LAUNCH("smoe_grouped_gemm/persistent-direct");
       return 0;
     }
@@ -1142,19 +1143,15 @@ int launch_ps(const void* A, const void* W, const float* bias, const int32_t* of
   if constexpr (!KEEP && sizeof(OT) == 4) {
     // f32 outputs (GEMM-2 with the fused combine + residual, the attention projection): the staged epilogue whose residual
     // loads and output stores go through buffer descriptors; every output row must end inside their 2 GiB
-    if (allow_direct && epilogue != SMOE_EPI_GELU_GRAD && out_rows > 0 && out_rows * (int64_t)N * 4 < (1ll << 31)) {
+    if (allow_direct && g.epilogue != SMOE_EPI_GELU_GRAD && g.out_rows > 0 && g.out_rows * (int64_t)g.N * 4 < (1ll << 31)) {
       SMOE_ENSURE_SMEM(grouped_gemm_ps<AB, OT, AFR, DEEP, false, false, true>);
-      hipLaunchKernelGGL((grouped_gemm_ps<AB, OT, AFR, DEEP, false, false, true>), dim3(grid), dim3(512), 160 * 1024, s,
-                         (const AB*)A, (const AB*)W, bias, offsets, group_expert, E, K, N, epilogue, row_map, row_scale,
-                         (const OT*)residual, (OT*)out, n_tiles_n, group_m, a_gather, a_div, (int)m_rows_max, group_end);
+      launch(grouped_gemm_ps<AB, OT, AFR, DEEP, false, false, true>);
       SMOE_CHECK_LAUNCH("smoe_grouped_gemm/persistent-buffer");
       return 0;
     }
   }
   SMOE_ENSURE_SMEM(grouped_gemm_ps<AB, OT, AFR, DEEP, KEEP>);
-  hipLaunchKernelGGL((grouped_gemm_ps<AB, OT, AFR, DEEP, KEEP>), dim3(grid), dim3(512), 160 * 1024, s, (const AB*)A, (const AB*)W,
-                     bias, offsets, group_expert, E, K, N, epilogue, row_map, row_scale, (const OT*)residual, (OT*)out,
-                     n_tiles_n, group_m, a_gather, a_div, (int)m_rows_max, group_end);
+  launch(grouped_gemm_ps<AB, OT, AFR, DEEP, KEEP>);
   SMOE_CHECK_LAUNCH("smoe_grouped_gemm/persistent");
   return 0;
 }

@@ -349,10 +349,7 @@ class FMoETransformerMLP(nn.Module):
         if is_switch:
             from .autograd import switch_aux_loss
             g.set_loss(switch_aux_loss(pruned if pruned is not None else idx, probs, g.tot_expert))
-        ex = self.experts
-        w1, w2 = ex.htoh4.weight_as(cd), ex.h4toh.weight_as(cd)
-        b1 = ex.htoh4.bias.detach().float() if ex.htoh4.bias is not None else None
-        b2 = ex.h4toh.bias.detach().float() if ex.h4toh.bias is not None else None
+        w1, b1, w2, b2 = operands = self.expert_operands(cd)
         if next_norm is not None and TAIL_MODE == "ln" and _tail_ln_ok(next_norm, x2, cd, k):
             # GEMM-2 stores plain 16-bit rows straight from its accumulators (the direct-store epilogue: no row map, no f32 residual
             # traffic on the CU's store path, which nothing overlaps with MFMAs), and ONE pass at the HBM roof then does the combine,
@@ -363,21 +360,37 @@ class FMoETransformerMLP(nn.Module):
             out, xn_next = ops.gather_combine_ln(y, inv_pos, score, T, k, x2, next_norm.weight.detach().float(),
                                                  next_norm.bias.detach().float(), next_norm.eps, torch.float16)
             return out.reshape(shape), xn_next.reshape(shape)
-        if k == 1:
-            out = x2.clone() if cap >= 0 else torch.empty_like(x2)
-            # both expert GEMMs (scatter folded into GEMM-1's operand fetch, combine + residual into GEMM-2's store) as ONE persistent
-            # launch; same arithmetic tile for tile as the two launches below, which remain for the shapes it does not cover
-            if not (ops.FFN_FUSED and self.gemm_variant == 9 and x2.dtype == torch.float32 and ops.expert_ffn(
-                    xn16, w1, b1, w2, b2, offsets, out, a_gather=pos, a_div=k, row_map=pos, row_scale=score.reshape(-1),
-                    residual=x2) is not None):
-                h = ops.grouped_gemm(xn16, w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant, a_gather=pos, a_div=k)
-                ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, x2.dtype, row_map=pos, row_scale=score.reshape(-1),
-                                 out=out, variant=self.gemm_variant, residual=x2)
-        else:
-            h = ops.grouped_gemm(xn16, w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant, a_gather=pos, a_div=k)
-            y = ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, cd, variant=self.gemm_variant)
-            out = ops.gather_combine(y, inv_pos, score, T, k, x2.dtype, residual=x2)
+        out = (x2.clone() if cap >= 0 else torch.empty_like(x2)) if k == 1 else None   # (k > 1: the combine allocates it)
+        out = self._gathered_tail(xn16, operands, cd, offsets, pos, inv_pos, score, residual=x2, out=out,
+                                  allow_fused=x2.dtype == torch.float32)
         return out.reshape(shape)
+
+    def expert_operands(self, cd: torch.dtype):
+        """``(w1, b1, w2, b2)`` as the grouped GEMM takes them: the weights' images in the compute dtype, the biases in f32."""
+        ex = self.experts
+        w1, w2 = ex.htoh4.weight_as(cd), ex.h4toh.weight_as(cd)
+        b1 = ex.htoh4.bias.detach().float() if ex.htoh4.bias is not None else None
+        b2 = ex.h4toh.bias.detach().float() if ex.h4toh.bias is not None else None
+        return w1, b1, w2, b2
+
+    def _gathered_tail(self, xn16, operands, cd, offsets, pos, inv_pos, score, residual, out, allow_fused=True):
+        """The single-rank expert FFN behind a fused norm + router pass: GEMM-1 gathers its rows from the un-permuted 16-bit image
+        ``xn16`` (the scatter folded into its operand fetch); for k = 1 GEMM-2's store does the combine and the residual add into
+        ``out``, else GEMM-2 is followed by the combine (into ``out``, or into a new tensor when it is None).  Returns the result."""
+        w1, b1, w2, b2 = operands
+        k = self.top_k
+        # k = 1: both expert GEMMs as ONE persistent launch (optional build, ops.FFN_FUSED); same arithmetic tile for tile as the
+        # two launches below, which remain for the shapes it does not cover
+        if (k == 1 and allow_fused and ops.FFN_FUSED and self.gemm_variant == 9 and ops.expert_ffn(
+                xn16, w1, b1, w2, b2, offsets, out, a_gather=pos, a_div=k, row_map=pos, row_scale=score.reshape(-1),
+                residual=residual) is not None):
+            return out
+        h = ops.grouped_gemm(xn16, w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant, a_gather=pos, a_div=k)
+        if k == 1:
+            return ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, residual.dtype, row_map=pos, row_scale=score.reshape(-1),
+                                    out=out, variant=self.gemm_variant, residual=residual)
+        y = ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, cd, variant=self.gemm_variant)
+        return ops.gather_combine(y, inv_pos, score, residual.shape[0], k, residual.dtype, residual=residual, out=out)
 
     # -- residual-MoE block half with the token-skip gate (models/resMoE.py:137-143) ---------------------------------
     def norm_gate_fusable(self, x: torch.Tensor, norm: nn.Module) -> bool:
@@ -467,21 +480,7 @@ class FMoETransformerMLP(nn.Module):
             return res.reshape(shape)
         counts, offsets, pos, inv_pos, _ = ops.dispatch_plan(r["idx_plan"], g.tot_expert, -1, hist=hist)
         self.last_plan = (idx, score, counts, offsets, pos, inv_pos)
-        ex = self.experts
-        w1, w2 = ex.htoh4.weight_as(cd), ex.h4toh.weight_as(cd)
-        b1 = ex.htoh4.bias.detach().float() if ex.htoh4.bias is not None else None
-        b2 = ex.h4toh.bias.detach().float() if ex.h4toh.bias is not None else None
-        if k == 1:
-            if not (ops.FFN_FUSED and self.gemm_variant == 9 and ops.expert_ffn(
-                    r["xn16"], w1, b1, w2, b2, offsets, out, a_gather=pos, a_div=k, row_map=pos, row_scale=score.reshape(-1),
-                    residual=out) is not None):
-                h = ops.grouped_gemm(r["xn16"], w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant, a_gather=pos, a_div=k)
-                ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, torch.float32, row_map=pos, row_scale=score.reshape(-1),
-                                 out=out, variant=self.gemm_variant, residual=out)
-        else:
-            h = ops.grouped_gemm(r["xn16"], w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant, a_gather=pos, a_div=k)
-            y = ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, cd, variant=self.gemm_variant)
-            ops.gather_combine(y, inv_pos, score, T, k, torch.float32, residual=out, out=out)
+        self._gathered_tail(r["xn16"], self.expert_operands(cd), cd, offsets, pos, inv_pos, score, residual=out, out=out)
         return out.reshape(shape)
 
     def forward(self, inp: torch.Tensor) -> torch.Tensor:
@@ -511,10 +510,7 @@ class FMoETransformerMLP(nn.Module):
                      row_scale=None, out_dtype=None, group_expert=None, residual=None, group_end=None, rows_hint=None):
         """``rows_hint``: with ``group_end`` (row ranges inside a padded buffer) the number of rows expected to exist -- what the
         GEMMs' tile height is chosen for, and what the profiler counts FLOPs over."""
-        ex = self.experts
-        w1, w2 = ex.htoh4.weight_as(cd), ex.h4toh.weight_as(cd)
-        b1 = ex.htoh4.bias.detach().float() if ex.htoh4.bias is not None else None
-        b2 = ex.h4toh.bias.detach().float() if ex.h4toh.bias is not None else None
+        w1, b1, w2, b2 = self.expert_operands(cd)
         if self._fused_gelu:
             h = ops.grouped_gemm(rows, w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant,
                                  group_expert=group_expert, group_end=group_end, rows_hint=rows_hint)

@@ -718,20 +718,6 @@ def set_reserved_cus(n: int) -> int:
     return prev
 
 
-def _ps_variant(rows: int, G: int, K: int, N: int, device) -> int:
-    """The persistent GEMM's tile height / schedule for ``rows`` real rows in G groups -- csrc/gemm.hip's variant-9 rule (expected
-    tiles of 256 or 320 rows, cost-weighted rounds of workgroups, ties to the taller tile; deep schedule for K >= 2048) as an
-    explicit variant: 10 / 11 = 320- / 256-row tiles, 13 / 12 = the same on the deep schedule."""
-    cus = torch.cuda.get_device_properties(device).multi_processor_count
-    ntn = -(-N // 256)
-    t256 = (-(-rows // 256) + G // 2) * ntn
-    t320 = (-(-rows // 320) + G // 2) * ntn
-    tall = -(-t320 // cus) * 1.25 <= -(-t256 // cus) * 1.0
-    if K >= 2048:
-        return 13 if tall else 12
-    return 10 if tall else 11
-
-
 def grouped_gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], offsets: torch.Tensor,
                  epilogue: int = EPI_NONE, out_dtype: Optional[torch.dtype] = None,
                  row_map: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None,
@@ -792,8 +778,8 @@ def grouped_gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor],
     rows = M if rows_hint is None else rows_hint
     if variant == 9 and group_end is not None and rows_hint is not None:
         # separate row ranges inside a PADDED buffer: the library picks tile height from the rows it is told about (M = the buffer);
-        # pick here, by the same cost-weighted rounds, from the rows that are expected to exist
-        variant = _ps_variant(int(rows_hint), G, K, N, A.device)
+        # ask it for its rule's answer (as an explicit variant, 10-13) for the rows that are expected to exist
+        variant = lib.smoe_grouped_gemm_plan(int(rows_hint), G, K, N)
     with _timed(prof_name, {"flops": 2.0 * rows * K * N, "K": K, "N": N, "epilogue": epilogue}, A):
         rc = lib.smoe_grouped_gemm(_ptr(A), _ptr(W), _ptr(bias), _ptr(offsets), _ptr(group_expert), G, E, M, K, N,
                                    dtype_code(A.dtype), epilogue, _ptr(row_map), _ptr(row_scale), _ptr(residual),

@@ -796,6 +796,69 @@ def test_persistent_gemm_equals_one_workgroup_per_tile_kernel_bitwise(variant):
         assert torch.equal(o_ps, o_ref)
 
 
+def _plan_rule(rows, G, K, N, cus):
+    """include/slimmoe.h's statement of the tile rule (smoe_grouped_gemm_plan), in integers: the explicit persistent variant."""
+    ceil = lambda a, b: -(-a // b)
+    t256, t320 = ((ceil(rows, h) + G // 2) * ceil(N, 256) for h in (256, 320))
+    tall = ceil(t320, cus) * 1.25 <= ceil(t256, cus)
+    if K >= 2048:
+        return 13 if tall else 12
+    return 10 if tall else 11
+
+
+# (rows, G, K, N); the comment = the outcome on 256 CUs (tiles of 256 / 320 rows -> rounds of workgroups)
+_PLAN_CASES = [(50432, 8, 768, 3072),       # 10: 2412 / 1944 tiles, 10 / 8 rounds, 8 * 1.25 == 10: the tie goes to the tall tile
+               (50432, 8, 3072, 768),       # 13: 603 / 486 tiles, 3 / 2 rounds; K >= 2048
+               (50432, 1, 768, 2304),       # 11: 1773 / 1422 tiles, 7 / 6 rounds, 7.5 > 7
+               (50432, 1, 2048, 2304),      # 12: the same tiles at K = 2048
+               (50432, 1, 1984, 2304),      # 11: K = 2047 rounded down to a multiple of 64
+               (50432, 1, 2112, 2304),      # 12: K = 2049 rounded up
+               (50432, 8, 1984, 768),       # 10: the K threshold on the tall tile, below ...
+               (50432, 8, 2048, 768),       # 13: ... and at it
+               (20224, 1, 768, 1024),       # 10: one group adds no expected tile (G // 2 == 0): 316 / 256 tiles, 2 / 1 rounds
+               (30000, 63, 768, 3072),      # 11: 31 expected extra m-tiles: 1788 / 1500 tiles, 7 / 6 rounds
+               (400, 3, 128, 264),          # 11: one round either way
+               (1, 1, 64, 8),               # 11: a single tile
+               (0, 1, 64, 8),               # 10: no tile at all: 0 * 1.25 <= 0
+               (2 ** 31 - 1, 63, 4096, 8192)]   # 12: 64-bit tile counts (268436448 / 214749376 tiles)
+
+
+def test_grouped_gemm_plan_is_the_library_rule():
+    """smoe_grouped_gemm_plan -- what ops.grouped_gemm asks for the static expert exchange's tile height -- is the rule the header
+    states: t = (ceil(rows / h) + G // 2) * ceil(N / 256) expected tiles of h rows, tall iff ceil(t320 / cus) * 1.25 <=
+    ceil(t256 / cus), deep iff K >= 2048.  The cases cover the four outcomes, a tie and the K threshold."""
+    assert {_plan_rule(*c, 256) for c in _PLAN_CASES} == {10, 11, 12, 13}
+    lib = sm._lib.load()
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    with torch.cuda.device(DEV):
+        got = [lib.smoe_grouped_gemm_plan(*c) for c in _PLAN_CASES]
+        print(f"cus = {cus}; plans = {got}")
+        assert got == [_plan_rule(*c, cus) for c in _PLAN_CASES]
+        if cus == 256:   # the benchmark model's GEMM-1, GEMM-2 and qkv: the instantiations bench.py names
+            assert lib.smoe_grouped_gemm_plan(50432, 8, 768, 3072) == 10
+            assert lib.smoe_grouped_gemm_plan(50432, 8, 3072, 768) == 13
+            assert lib.smoe_grouped_gemm_plan(50432, 1, 768, 2304) == 11
+
+
+def test_auto_variant_equals_its_planned_variant_bitwise():
+    """The variant table from the outside: the auto variant of each family (9 persistent, 4 one workgroup per tile) gives the bits
+    of the explicit variant smoe_grouped_gemm_plan names -- the same column of the other family's row for 4."""
+    counts = [70, 0, 330]
+    E, K, N = len(counts), 128, 264
+    offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), device=DEV)
+    M = int(offsets[-1])
+    g = _gen(9)
+    a = torch.randn(M, K, generator=g).half().to(DEV)
+    w = (torch.randn(E, N, K, generator=g) * 0.05).half().to(DEV)
+    bias = (torch.randn(E, N, generator=g) * 0.1).to(DEV)
+    with torch.cuda.device(DEV):
+        plan = sm._lib.load().smoe_grouped_gemm_plan(M, E, K, N)
+    assert plan in (10, 11, 12, 13)
+    run = lambda v: ops.grouped_gemm(a, w, bias, offsets, ops.EPI_GELU, torch.float16, variant=v)
+    assert torch.equal(run(9), run(plan))
+    assert torch.equal(run(4), run(plan - 9 + 4))
+
+
 @pytest.mark.parametrize("N", [256, 512, 768, 1024, 1280])
 @pytest.mark.parametrize("K", [256, 2048])
 def test_persistent_gemm_f32_epilogue_and_tile_orders_bitwise(N, K):
