@@ -167,6 +167,106 @@ def dispatch_plan(idx, E: int, capacity: int = -1) -> Plan:
     return Plan(counts, offsets, pos, inv, flat)
 
 
+@dataclass
+class SlotPlan:
+    counts: np.ndarray      # int32 [E]   kept entries per expert
+    offsets: np.ndarray     # int32 [E+1] exclusive prefix of counts (the compact layout's offsets)
+    group_end: np.ndarray   # int32 [E]   slot_base[e] + counts[e]
+    pos_slots: np.ndarray   # int64 [slot_base[E]] slot -> flat index, -1 where unused (header rows included)
+    inv_pos: np.ndarray     # int64 [n]   flat index -> slot, -1 if dropped
+    idx_pruned: np.ndarray  # int64 [n]   expert id or -1
+    raw_counts: np.ndarray  # int32 [E]   entries routed to each expert before any clamp
+
+
+def dispatch_plan_slots(idx, E: int, slot_base, hdr_rows: int = 1, capacity: int = -1) -> SlotPlan:
+    """The plan over a slot table (the static expert exchange's send layout): expert e owns the slots
+    [slot_base[e], slot_base[e + 1]), the last ``hdr_rows`` of which carry no payload.  In ascending flat index, entry i with
+    expert e is kept iff its raw rank among e's entries is below min(max(region - hdr_rows, 0), capacity if capacity >= 0 else
+    inf); a kept entry takes the slot slot_base[e] + rank.  Ids outside [0, E) are dropped and not counted in raw_counts."""
+    flat = np.asarray(idx, dtype=np.int64).reshape(-1)
+    base = np.asarray(slot_base, dtype=np.int64).reshape(-1)
+    assert base.size == E + 1
+    n = flat.size
+    room = []
+    for e in range(E):
+        c = max(int(base[e + 1] - base[e]) - hdr_rows, 0)
+        if capacity is not None and capacity >= 0:
+            c = min(c, int(capacity))
+        room.append(c)
+    raw = np.zeros(E, dtype=np.int32)
+    counts = np.zeros(E, dtype=np.int32)
+    pos = np.full(int(base[E]), -1, dtype=np.int64)
+    inv = np.full(n, -1, dtype=np.int64)
+    pruned = np.full(n, -1, dtype=np.int64)
+    for i in range(n):  # ascending flat index
+        e = int(flat[i])
+        if e < 0 or e >= E:
+            continue
+        rank = int(raw[e])
+        raw[e] += 1
+        if rank < room[e]:
+            slot = int(base[e]) + rank
+            pos[slot] = i
+            inv[i] = slot
+            pruned[i] = e
+            counts[e] += 1
+    offsets = np.zeros(E + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(counts)
+    group_end = (base[:-1] + counts).astype(np.int32)
+    return SlotPlan(counts, offsets, group_end, pos, inv, pruned, raw)
+
+
+HEADER_FIXED_WORDS = 4  # {kept, raw, T, G} in front of the G raw counts
+
+
+def pack_headers_ref(send_bytes, counts, raw_counts, slot_base, t_rows: int) -> np.ndarray:
+    """Expected bytes of a static-exchange send buffer after the header write.  ``send_bytes``: uint8 [rows, row_bytes], the
+    buffer before the write.  The last row of every region [slot_base[g], slot_base[g + 1]) gets the little-endian int32 words
+    {counts[g], raw[g], t_rows, G, raw[0], ..., raw[G - 1]} at its start -- 4 + G words, nothing else changes.  ``raw_counts``
+    None: raw = counts; ``counts`` None as well (a rank without rows): all zero."""
+    out = np.array(send_bytes, dtype=np.uint8, copy=True)
+    base = np.asarray(slot_base, dtype=np.int64).reshape(-1)
+    G = base.size - 1
+    c = np.zeros(G, dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32).reshape(-1)
+    r = c if raw_counts is None else np.asarray(raw_counts, dtype=np.int32).reshape(-1)
+    for g in range(G):
+        words = np.concatenate([np.array([c[g], r[g], t_rows, G], dtype=np.int32), r]).astype("<i4")
+        assert words.size == HEADER_FIXED_WORDS + G
+        row = int(base[g + 1]) - 1
+        out[row, :4 * words.size] = words.view(np.uint8)
+    return out
+
+
+def unpack_headers_ref(recv_bytes, W: int, local_base, E_total: int):
+    """(starts i32 [W * E_local], ends i32 [W * E_local], stats i32 [W, 1 + E_total]) from a received static-exchange buffer
+    (uint8 [W * local_base[-1], row_bytes]): source w's block holds this rank's E_local regions, region e' = rows
+    [local_base[e'], local_base[e' + 1]) of the block with its header in the last row.  Group l = w * E_local + e' holds the
+    rows [start, start + kept) with the header's kept count clamped to [0, region - 1].  stats[w] = (T, raw[0 .. E_total)) from
+    the header of source w's first region; the raw entries are -1 when the header's word 3 is not E_total."""
+    buf = np.asarray(recv_bytes, dtype=np.uint8)
+    lb = np.asarray(local_base, dtype=np.int64).reshape(-1)
+    E_local = lb.size - 1
+    block = int(lb[E_local])
+    starts = np.zeros(W * E_local, dtype=np.int32)
+    ends = np.zeros(W * E_local, dtype=np.int32)
+    stats = np.zeros((W, 1 + E_total), dtype=np.int32)
+
+    def header(row):
+        return np.ascontiguousarray(buf[row]).view("<i4")
+
+    for w in range(W):
+        for e in range(E_local):
+            r0, r1 = w * block + int(lb[e]), w * block + int(lb[e + 1])
+            kept = int(header(r1 - 1)[0])
+            kept = min(max(kept, 0), r1 - r0 - 1)
+            starts[w * E_local + e] = r0
+            ends[w * E_local + e] = r0 + kept
+        h = header(w * block + int(lb[1]) - 1)
+        stats[w, 0] = h[2]
+        stats[w, 1:] = h[4:4 + E_total] if int(h[3]) == E_total else -1
+    return starts, ends, stats
+
+
 # --------------------------------------------------------------------------- experts
 def gelu_erf(h: torch.Tensor) -> torch.Tensor:
     """nn.GELU() default = exact erf form (resMoE.py:23 act_layer=th.nn.GELU)."""

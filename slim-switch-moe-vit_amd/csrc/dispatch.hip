@@ -191,7 +191,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void plan_assign_kernel(
     const int64_t i = wave_base + it * 64 + lane;
     int64_t e = -1;
     if (i < n) e = idx[i];
-    if (e >= E) e = -1;
+    if (e >= E || e < 0) e = -1;                  // (before pass 2 narrows it to int: the low word of a 64-bit id outside [0, E) may lie inside)
     myidx[it] = e;
     if (e >= 0) atomicAdd(&run[wave * E + (int)e], 1);
   }
@@ -515,17 +515,19 @@ static int plan_impl(const int64_t* idx, int64_t n, int E, int64_t capacity, int
   const size_t per = (((size_t)nblk * (size_t)E * 4) + 15) & ~(size_t)15;
   int32_t* blockcnt = reinterpret_cast<int32_t*>((char*)workspace + 16);
   int32_t* rawbase = reinterpret_cast<int32_t*>((char*)workspace + 16 + per);
+  // the padded layouts exist in the fused kernel only: refused here, before anything is launched
+  const bool fused = n > 0 && E <= PLAN_FUSED_E && nblk * E <= PLAN_FUSED_MAX;
+  SMOE_REQUIRE(fused || (slot_stride == 0 && !slot_base), "smoe_dispatch_plan_padded / _slots: the padded layouts need E <= %d and ceil(n / %d) * E <= %d",
+               PLAN_FUSED_E, PLAN_CH, PLAN_FUSED_MAX);
   hipLaunchKernelGGL(plan_count_kernel, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)E * 4, s, idx, n, E, blockcnt);
   SMOE_CHECK_LAUNCH("smoe_dispatch_plan/count");
-  if (n > 0 && E <= PLAN_FUSED_E && nblk * E <= PLAN_FUSED_MAX) {
+  if (fused) {
     hipLaunchKernelGGL(plan_assign_kernel<true>, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)(PLAN_WAVES * E + 5 * E + 2) * 4, s,
                        idx, n, E, capacity, blockcnt, nullptr, pos, inv_pos, idx_pruned, (int)nblk, counts, offsets, slot_stride,
                        group_end, (int)nblk, 1, raw_counts, slot_base, hdr_rows);
     SMOE_CHECK_LAUNCH("smoe_dispatch_plan/assign_fused");
     return 0;
   }
-  SMOE_REQUIRE(slot_stride == 0 && !slot_base, "smoe_dispatch_plan_padded / _slots: the padded layouts need E <= %d and ceil(n / %d) * E <= %d",
-               PLAN_FUSED_E, PLAN_CH, PLAN_FUSED_MAX);
   const int scan_threads = E < 64 ? 64 : (E > 1024 ? 1024 : ((E + 63) / 64) * 64);
   hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(scan_threads), (size_t)E * 4, s, blockcnt, (int)nblk, E, capacity, rawbase, counts, offsets);
   SMOE_CHECK_LAUNCH("smoe_dispatch_plan/scan");

@@ -58,6 +58,41 @@ def test_argument_validation_errors_come_back_as_messages():
     assert rc != 0 and b"out_rows" in lib.smoe_last_error()
 
 
+def test_static_exchange_entry_points_refuse_bad_arguments_before_any_launch():
+    """The slot plan, the header kernels and smoe_split_offsets check their arguments first: every case below comes back as a
+    message, with pointers that are never dereferenced (safe without a GPU)."""
+    lib = _lib.load()
+    fake = 4096
+    big = 1 << 30                                          # "workspace bytes": enough for every size below
+
+    def slots(n, E, table=fake, hdr_rows=1):
+        return lib.smoe_dispatch_plan_slots(fake, n, E, -1, table, hdr_rows, fake, fake, fake, fake, fake, fake, fake, fake, big, None)
+
+    assert slots(100, 8, hdr_rows=2) != 0 and b"hdr_rows" in lib.smoe_last_error()
+    assert slots(100, 8, hdr_rows=-1) != 0 and b"hdr_rows" in lib.smoe_last_error()
+    assert slots(100, 8, table=None) != 0 and b"slot table" in lib.smoe_last_error()
+    # the fused kernel's table: E <= 64 and ceil(n / 1024) * E <= 8192 -- n = 131072 at E = 64 is the last size that fits
+    for n, E in ((131073, 64), (1000, 65), (8192 * 1024 + 1, 1)):
+        assert slots(n, E) != 0, (n, E)
+        msg = lib.smoe_last_error()
+        assert b"E <= 64" in msg and b"8192" in msg, msg
+        rc = lib.smoe_dispatch_plan_padded(fake, n, E, 4, 4, fake, fake, fake, fake, fake, fake, None, fake, big, None)
+        assert rc != 0 and b"E <= 64" in lib.smoe_last_error(), (n, E)
+    with pytest.raises(_lib.SlimMoEError, match="padded layouts need"):
+        _lib.check(slots(131073, 64), "smoe_dispatch_plan_slots")
+    # a header holds 4 + G int32 words: the row must have room for them
+    rc = lib.smoe_ep_pack_headers(fake, fake, fake, 8, 16 + 4 * 8 - 4, 10, fake, None)
+    assert rc != 0 and b"row_bytes=44" in lib.smoe_last_error()
+    rc = lib.smoe_ep_pack_headers(fake, fake, None, 8, 48, 10, fake, None)
+    assert rc != 0 and b"null" in lib.smoe_last_error()
+    rc = lib.smoe_ep_unpack_headers(fake, 2, 4, fake, 16 + 4 * 8 - 4, 8, fake, fake, None, None)
+    assert rc != 0 and b"row_bytes=44" in lib.smoe_last_error()
+    rc = lib.smoe_ep_unpack_headers(fake, 2, 4, fake, 48, 8, None, fake, None, None)
+    assert rc != 0 and b"null" in lib.smoe_last_error()
+    rc = lib.smoe_split_offsets(fake, 4, 0, fake, None)
+    assert rc != 0 and b"S=0" in lib.smoe_last_error()
+
+
 def test_product_path_refuses_cpu_tensors():
     """No CPU fallback: the shipped module raises instead of silently computing elsewhere."""
     m = sm.CustomizedMoEMLP(32, 64, 4, 1, 0.0).eval()

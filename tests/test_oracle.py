@@ -104,6 +104,80 @@ def test_capacity_prune_keeps_first_tokens():
     assert mo.switch_capacity(1.0, 50432, 1, 8) == 6304
 
 
+@pytest.mark.parametrize("n,E,c", [(1, 4, 1), (257, 6, 30), (1000, 8, 100), (3000, 27, 64), (500, 3, 0)])
+def test_slot_plan_with_uniform_caps_keeps_what_the_capacity_plan_keeps(n, E, c):
+    """Regions of c payload rows + one header row: the slot plan keeps exactly the entries dispatch_plan(idx, E, c) keeps, in the
+    same order inside each expert; only the slot numbering differs (slot_base[e] + rank instead of offsets[e] + rank)."""
+    rng = np.random.default_rng(n + E)
+    idx = rng.integers(-1, E, size=n).astype(np.int64)
+    idx[rng.random(n) < 0.3] = 0          # an overloaded expert: drops
+    base = np.arange(E + 1) * (c + 1)
+    s = mo.dispatch_plan_slots(idx, E, base, hdr_rows=1)
+    p = mo.dispatch_plan(idx, E, c)
+    assert np.array_equal(s.idx_pruned, p.idx_pruned)
+    assert np.array_equal(s.counts, p.counts) and np.array_equal(s.offsets, p.offsets)
+    assert s.counts.dtype == np.int32 and s.group_end.dtype == np.int32 and s.raw_counts.dtype == np.int32
+    assert np.array_equal(s.raw_counts, np.bincount(idx[idx >= 0], minlength=E))
+    assert np.array_equal(s.group_end, base[:-1] + p.counts)
+    for e in range(E):
+        seg = p.pos[p.offsets[e]:p.offsets[e + 1]]
+        assert np.array_equal(s.pos_slots[base[e]:base[e] + len(seg)], seg)
+        assert np.all(s.pos_slots[base[e] + len(seg):base[e + 1]] == -1)      # unused payload slots and the header row
+        assert np.array_equal(s.inv_pos[seg], base[e] + np.arange(len(seg)))
+    assert np.all(s.inv_pos[p.idx_pruned < 0] == -1)
+    # a gate capacity on top of the slots is the smaller of the two; without header rows the whole region is payload
+    t = mo.dispatch_plan_slots(idx, E, base, hdr_rows=1, capacity=max(c - 1, 0))
+    assert np.array_equal(t.idx_pruned, mo.dispatch_plan(idx, E, max(c - 1, 0)).idx_pruned)
+    u = mo.dispatch_plan_slots(idx, E, base, hdr_rows=0)
+    assert np.array_equal(u.idx_pruned, mo.dispatch_plan(idx, E, c + 1).idx_pruned)
+
+
+def test_slot_plan_hand_worked_case():
+    """idx = [3, 3, 3, 0, 3, 0, -1, 2], E = 4, caps [1, 1, 2, 3], one header row per region.
+    Regions are caps + 1 = [2, 2, 3, 4] rows: slot_base = [0, 2, 4, 7, 11], payload room = caps.
+    Expert 0 gets entries 3, 5 (raw 2): entry 3 has rank 0 < 1 -> slot 0; entry 5 has rank 1 -> dropped.
+    Expert 1 gets nothing.  Expert 2 gets entry 7 (raw 1): rank 0 < 2 -> slot 4.
+    Expert 3 gets entries 0, 1, 2, 4 (raw 4): ranks 0, 1, 2 < 3 -> slots 7, 8, 9; entry 4 has rank 3 -> dropped.
+    Entry 6 (-1) belongs to nobody.  Slots 1, 3, 6, 10 are the header rows, 2 and 5 unused payload: all -1."""
+    s = mo.dispatch_plan_slots([3, 3, 3, 0, 3, 0, -1, 2], 4, [0, 2, 4, 7, 11], hdr_rows=1)
+    assert s.raw_counts.tolist() == [2, 0, 1, 4]
+    assert s.counts.tolist() == [1, 0, 1, 3]
+    assert s.offsets.tolist() == [0, 1, 1, 2, 5]
+    assert s.group_end.tolist() == [1, 2, 5, 10]
+    assert s.pos_slots.tolist() == [3, -1, -1, -1, 7, -1, -1, 0, 1, 2, -1]
+    assert s.inv_pos.tolist() == [7, 8, 9, 0, -1, -1, -1, 4]
+    assert s.idx_pruned.tolist() == [3, 3, 3, 0, -1, -1, -1, 2]
+    # ids outside [0, E) are dropped and not counted; an empty region and a header-only region keep nothing
+    t = mo.dispatch_plan_slots([4, 1, -2, 0, 2, 1], 3, [0, 0, 1, 3], hdr_rows=1)
+    assert t.raw_counts.tolist() == [1, 2, 1] and t.counts.tolist() == [0, 0, 1]
+    assert t.pos_slots.tolist() == [-1, 4, -1] and t.inv_pos.tolist() == [-1, -1, -1, -1, 1, -1]
+
+
+def test_header_reference_pack_then_unpack():
+    """The header wire format on the CPU: {kept, raw, T, G, raw[0 .. G)} as int32 words at the start of each region's last row,
+    every other byte left alone; the receiver clamps a count to [0, region - 1] and refuses the raw vector of a foreign G."""
+    caps, E_local, W = [3, 1, 2, 5], 2, 2
+    base = np.concatenate([[0], np.cumsum(np.array(caps) + 1)])
+    row_bytes = 16 + 4 * len(caps)
+    blank = np.full((int(base[-1]), row_bytes), 0xA5, dtype=np.uint8)
+    counts, raw = [3, 0, 2, 4], [7, 0, 2, 4]
+    sent = mo.pack_headers_ref(blank, counts, raw, base, 13)
+    hdr_rows = base[1:] - 1
+    assert np.all(np.delete(sent, hdr_rows, axis=0) == 0xA5)
+    assert sent[hdr_rows[2]].view("<i4").tolist() == [2, 2, 13, 4, 7, 0, 2, 4]
+    assert np.array_equal(mo.pack_headers_ref(blank, counts, None, base, 13)[hdr_rows[0]].view("<i4"), [3, 3, 13, 4, 3, 0, 2, 4])
+    assert np.array_equal(mo.pack_headers_ref(blank, None, None, base, 0)[hdr_rows[3]].view("<i4"), [0, 0, 0, 4, 0, 0, 0, 0])
+    # rank 1 (experts 2, 3) receives its regions from two sources that sent the same buffer
+    lb = base[2:] - base[2]
+    recv = np.concatenate([sent[base[2]:], sent[base[2]:]])
+    recv[int(lb[1]) - 1 + int(lb[2])].view("<i4")[0] = 99            # source 1, expert 2: a count above the region
+    recv[int(lb[2]) - 1 + int(lb[2])].view("<i4")[0] = -4            # source 1, expert 3: a negative count
+    starts, ends, stats = mo.unpack_headers_ref(recv, W, lb, 4)
+    assert starts.tolist() == [0, 3, 9, 12] and ends.tolist() == [2, 7, 11, 12]
+    assert stats.tolist() == [[13, 7, 0, 2, 4]] * 2
+    assert mo.unpack_headers_ref(recv, W, lb, 3)[2].tolist() == [[13, -1, -1, -1]] * 2
+
+
 def test_naive_top1_score_is_exactly_one_and_ties_pick_lowest_id():
     x = torch.zeros(5, 16)  # all-zero rows: logits == bias
     wg = torch.randn(4, 16)
