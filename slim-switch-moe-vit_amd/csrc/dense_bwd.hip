@@ -456,7 +456,7 @@ extern "C" int smoe_gate_ln_bwd(const float* x, const void* g_f, int g_f_dtype, 
   SMOE_REQUIRE(out && workspace && gate_w, "smoe_gate_ln_bwd: null pointer");
   SMOE_REQUIRE(workspace_bytes >= smoe_gate_ln_bwd_workspace_bytes(T, d), "smoe_gate_ln_bwd: workspace too small");
   SMOE_REQUIRE(T == 0 || (x && g_f && dx), "smoe_gate_ln_bwd: null pointer");
-  SMOE_REQUIRE(!gate_on || mask, "smoe_gate_ln_bwd: an enabled gate needs the forward's decisions (mask)");
+  SMOE_REQUIRE(T == 0 || !gate_on || mask, "smoe_gate_ln_bwd: an enabled gate needs the forward's decisions (mask)");   // (an empty mask has no address)
   SMOE_REQUIRE(smoe_dtype_ok(g_f_dtype), "smoe_gate_ln_bwd: bad g_f dtype");
   hipStream_t s = (hipStream_t)stream;
   float* partial = reinterpret_cast<float*>(workspace);
