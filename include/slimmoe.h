@@ -284,8 +284,11 @@ int smoe_gather_combine_ln(const void* y, int y_dtype, const int64_t* inv_pos, c
  * multiplied by row_scale[row_map[r]] if row_scale != NULL  (MOEGather + bmm for k = 1).
  * Optional fused residual (residual != NULL, same dtype / shape as out): the stored value is
  * residual[orow, :] + value -- the `x + mlp(norm2(x))` add of models/vision_transformer.py:321.
- * Optional fused scatter (a_gather != NULL; variants 4-8): row r of the GEMM reads A[a_gather[r] / a_div, :]
+ * Optional fused scatter (a_gather != NULL; variants 4-14): row r of the GEMM reads A[a_gather[r] / a_div, :]
  * instead of A[r, :] -- MOEScatter's index_select(x, pos // k) folded into the operand DMA (A = the token matrix).
+ * The library never learns how many rows that A has (m_rows_max counts the gathered rows): with a_gather the persistent
+ * variants 9-14 need ALL of A under 4 GiB -- the caller's duty; their 32-bit byte offsets would otherwise read rows modulo 2^32
+ * with no error.  Variants 4-8 hold 64-bit row pointers and take any A (the Python wrapper sends a larger A there).
  * SMOE_EPI_GELU_GRAD (backward of the activation, fused into the dgrad GEMM): `residual` then holds the saved
  * pre-activations H and the stored value is value * gelu'(H[r, :]).
  * Optional group -> expert map (group_expert != NULL, i32 [G]): `offsets` then delimits G row groups and
@@ -333,7 +336,9 @@ int smoe_grouped_gemm_plan(int64_t rows, int G, int K, int N);
  * a_gather / row_map / row_scale / residual / b1 / b2 / group_expert may be NULL.  `workspace`: smoe_expert_ffn_workspace_bytes
  * bytes, ZERO before the first launch; every launch leaves it zero again (word 17 = error flag: set if a wait on a row counter ran
  * out -- never in a healthy launch).  Returns -1 (no error set) for shapes outside this launch's reach (operands not f16 / bf16,
- * out not f32, d_in or d_hidden % 64, > 63 groups, operands >= 4 GiB, out >= 2 GiB): issue the two smoe_grouped_gemm then. */
+ * out not f32, d_in or d_hidden % 64, > 63 groups, operands >= 4 GiB, out >= 2 GiB): issue the two smoe_grouped_gemm then.
+ * With a_gather ALL of X must be under 4 GiB (the caller's duty, as for smoe_grouped_gemm's variants 9-14: the row count of X is
+ * not an argument). */
 size_t smoe_expert_ffn_workspace_bytes(int64_t m_rows_max, int G);
 int smoe_expert_ffn(const void* X, const int64_t* a_gather, int a_div, const void* W1, const float* b1, void* H, const void* W2,
                     const float* b2, const int32_t* offsets, const int32_t* group_expert, int G, int n_experts,

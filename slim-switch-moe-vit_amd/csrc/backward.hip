@@ -576,6 +576,8 @@ extern "C" int smoe_transpose_pad(const void* src, int dtype, const int32_t* off
   SMOE_REQUIRE(E >= 1 && C > 0 && Lp > 0 && Lp % 64 == 0 && (int64_t)Lp >= ((n_rows + 63) / 64) * 64,
                "smoe_transpose_pad: bad sizes (Lp=%d must be a multiple of 64 and >= padded rows)", Lp);
   SMOE_REQUIRE(dtype == SMOE_F16 || dtype == SMOE_BF16 || dtype == SMOE_F32, "smoe_transpose_pad: bad dtype");
+  // one grid row per 64 padded token rows: the grid's second dimension ends at 65,535
+  SMOE_REQUIRE(Lp / 64 <= 65535, "smoe_transpose_pad: Lp=%d is past the limit of 65535 x 64 = 4194240 padded rows", Lp);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((C + 63) / 64, Lp / 64);
   if (dtype == SMOE_F32) {
@@ -603,7 +605,8 @@ extern "C" int smoe_group_colsum(const void* src, int dtype, const int32_t* offs
                "smoe_group_colsum: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int64_t chunks = colsum_chunks(n_rows_max, E);
-  SMOE_REQUIRE(chunks <= 65535, "smoe_group_colsum: too many rows (%lld)", (long long)n_rows_max);
+  SMOE_REQUIRE(chunks <= 65535, "smoe_group_colsum: too many rows (%lld): the limit is 65535 chunks of %d rows, one per row group included",
+               (long long)n_rows_max, (int)CS_ROWS);
   float* partial = reinterpret_cast<float*>(workspace);
   const bool wide = dtype != SMOE_F32 && C % 8 == 0;     // 16-byte loads: 8 elements of a 16-bit row
   const int slab = 64 * (wide ? 8 : 4);
@@ -643,7 +646,7 @@ extern "C" int smoe_gate_wgrad(const float* dl, const void* x, int x_dtype, int6
   SMOE_REQUIRE(dl && x, "smoe_gate_wgrad: null pointer");
   SMOE_REQUIRE(workspace && workspace_bytes >= smoe_gate_wgrad_workspace_bytes(n_rows, E, C), "smoe_gate_wgrad: workspace too small");
   const int64_t chunks = (n_rows + GW_ROWS - 1) / GW_ROWS;
-  SMOE_REQUIRE(chunks <= 65535, "smoe_gate_wgrad: too many rows (%lld)", (long long)n_rows);
+  SMOE_REQUIRE(chunks <= 65535, "smoe_gate_wgrad: too many rows (%lld): the limit is 65535 chunks of %d rows", (long long)n_rows, (int)GW_ROWS);
   float* partial = reinterpret_cast<float*>(workspace);
   float* bpart = db ? partial + (size_t)chunks * E * C : nullptr;
   dim3 grid1((C + CS_COLS - 1) / CS_COLS, (unsigned)chunks), grid2((C + 63) / 64, E);
@@ -726,7 +729,7 @@ extern "C" int smoe_transpose_cast(const void* src, int src_dtype, void* dst, in
   SMOE_REQUIRE(src && dst, "smoe_transpose_cast: null pointer");
   SMOE_REQUIRE(smoe_dtype_ok(src_dtype) && smoe_dtype_ok(dst_dtype), "smoe_transpose_cast: bad dtype");
   SMOE_REQUIRE(B >= 1 && B <= 65535 && R > 0 && C > 0 && R % 64 == 0 && C % 64 == 0 && R / 64 <= 65535,
-               "smoe_transpose_cast: B=%d R=%d C=%d (R and C must be multiples of 64)", B, R, C);
+               "smoe_transpose_cast: B=%d R=%d C=%d (R and C must be multiples of 64; the limit is B <= 65535 and R <= 65535 x 64)", B, R, C);
   hipStream_t s = (hipStream_t)stream;
   switch (src_dtype) {
     case SMOE_F32: return transpose_cast_launch<float>(src, dst, dst_dtype, B, R, C, s);

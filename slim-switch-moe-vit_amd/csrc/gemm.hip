@@ -700,9 +700,12 @@ __global__ __launch_bounds__(512, 2) void grouped_gemm_pp256(
   const AB* w_src[SLOTS];
   // per K-tile advance of the source pointers (elements): 64 k-columns, or 64 token rows in MODE 2
   const int64_t a_step = (MODE == 2) ? (int64_t)64 * m_rows : 64, w_step = (MODE == 2) ? (int64_t)64 * N : 64;
-  // MODE 2: 32-bit ELEMENT offsets from A / W instead of per-lane pointers (the launcher keeps both operands under 2^32
-  // elements), and ONE running row offset + first column per operand -- slot s reads 64 s columns further, clamped at the
-  // matrix edge when its piece is issued: the 320-row tile has no registers to spare for nine 64-bit running pointers
+  // MODE 2: 32-bit ELEMENT offsets from A / W instead of per-lane pointers.  Both operands must stay under 2^32 elements; no C
+  // launcher can see to that (smoe_grouped_wgrad_rows takes no row count): the caller keeps the bound, as the Python wrapper
+  // ops.grouped_wgrad_rows does by sending larger operands to the K-major path.  Rows of the last K-tile past the range may wrap;
+  // they are replaced by the zero page below before they are read.
+  // Each operand has ONE running row offset and one first column.  Slot s reads 64 s columns further, clamped at the matrix edge
+  // when its piece is issued: the 320-row tile has no registers to spare for nine 64-bit running pointers.
   uint32_t a_rowoff = 0, w_rowoff = 0;
   int a_col0 = 0, w_col0 = 0;
   const int t_row = 8 * wave + l_row;  // MODE 2: token row (inside the K-tile) this lane stages, the same in every slot

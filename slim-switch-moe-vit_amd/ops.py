@@ -776,6 +776,14 @@ def grouped_gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor],
             raise RuntimeError("residual: expected the shape of out")
     lib = _lib.load()
     rows = M if rows_hint is None else rows_hint
+    if a_gather is not None and 9 <= variant <= 14 and A.numel() * A.element_size() >= 2 ** 32:
+        # the persistent kernel addresses A with 32-bit BYTE offsets and the library sees a_gather.numel() rows, not A's: a gathered
+        # row of an A of 4 GiB or more would be read modulo 2^32.  The same plan runs in the one-workgroup-per-tile family
+        # (64-bit row pointers), as the library itself chooses for an ungathered A of that size.
+        if group_end is not None:
+            raise RuntimeError("grouped_gemm: group_end needs the persistent kernel, and with a_gather that kernel needs all of A "
+                               f"under 4 GiB (A is {tuple(A.shape)} {A.dtype})")
+        variant = 4 if variant in (9, 14) else variant - 5
     if variant == 9 and group_end is not None and rows_hint is not None:
         # separate row ranges inside a PADDED buffer: the library picks tile height from the rows it is told about (M = the buffer);
         # ask it for its rule's answer (as an explicit variant, 10-13) for the rows that are expected to exist
@@ -861,6 +869,8 @@ def expert_ffn(X: torch.Tensor, W1: torch.Tensor, b1: Optional[torch.Tensor], W2
             raise RuntimeError("residual: expected the shape of out")
     if X.dtype not in (torch.float16, torch.bfloat16) or M == 0:
         return None
+    if a_gather is not None and X.numel() * X.element_size() >= 2 ** 32:
+        return None     # 32-bit byte offsets into X, of which the library sees a_gather.numel() rows only: the two launches handle it
     if not ffn_fused_available():
         raise _lib.SlimMoEError("smoe_expert_ffn is not in this build of libslimmoe_hip.so (it measured slower than the two launches and "
                                 "left the default build in round 5): make -C slim-switch-moe-vit_amd/csrc FFN=-DSMOE_FFN_FUSED")
@@ -1143,7 +1153,9 @@ def grouped_wgrad_rows(P: torch.Tensor, Q: torch.Tensor, offsets: torch.Tensor, 
     R1, R2 = P.shape[1], Q.shape[1]
     if P.numel() >= 2 ** 32 or Q.numel() >= 2 ** 32:
         # the token-major kernel addresses its operands with 32-bit ELEMENT offsets (csrc/gemm.hip MODE 2): an operand of
-        # 2^32 elements or more takes the K-major path (64-padded transposed images, 64-bit row bases)
+        # 2^32 elements or more takes the K-major path (64-padded transposed images, 64-bit row bases).  That path ends at
+        # smoe_transpose_pad's own limit of 4,194,240 padded rows (its grid's second dimension): operands of 1,024 columns or fewer
+        # have more rows than that by the time they hold 2^32 elements, and get its error instead of a result.
         offs_pad = pad_offsets(offsets)
         Lp = padded_len(P.shape[0], E)
         return grouped_wgrad(transpose_pad(P, offsets, offs_pad, Lp), transpose_pad(Q, offsets, offs_pad, Lp), offs_pad)
