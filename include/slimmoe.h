@@ -156,11 +156,19 @@ int smoe_depth_scale_rows(const float* mask, float keep, int64_t B, int N, float
  *                      f32 residual stream [B, P + 1, d] -- and, when xn != NULL, xn = LayerNorm(x32) in f16 / bf16 (block 0's norm1)
  *                      from the same pass.  tokens [B * P, d] f16 / bf16 (the projection GEMM's output), cls_token [d], pos_embed
  *                      [P + 1, d], gamma / beta [d] f32; d in {192, 384, 768, 1024}
+ * smoe_embed_ln2:      smoe_embed_ln with a second prefix row, the distillation token of DeiT's DistilledVisionTransformer
+ *                      (models/model.py:48-67): x32[b, 0] = cls_token + pos_embed[0], x32[b, 1] = dist_token + pos_embed[1],
+ *                      x32[b, n] = tokens[b * P + n - 2] + pos_embed[n] (n = 2 .. P + 1) -- the stream [B, P + 2, d], pos_embed
+ *                      [P + 2, d] -- and the optional LayerNorm as above.  dist_token == NULL: one prefix row, the launch and the bits
+ *                      of smoe_embed_ln.
  * smoe_layernorm_rows: LayerNorm of T f32 rows that start row_stride elements apart (the class-token rows x[:, 0] behind the last
  *                      block: row_stride = (P + 1) * d); out f32 [T, d]                                                              */
 int smoe_patchify_cast(const float* images, int64_t B, int C, int H, int W, int ph, int pw, void* out, int out_dtype, void* stream);
 int smoe_embed_ln(const void* tokens, int tok_dtype, const float* cls_token, const float* pos_embed, const float* ln_gamma,
                   const float* ln_beta, float ln_eps, int64_t B, int P, int d, float* x32, void* xn, int xn_dtype, void* stream);
+int smoe_embed_ln2(const void* tokens, int tok_dtype, const float* cls_token, const float* dist_token, const float* pos_embed,
+                   const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t B, int P, int d, float* x32, void* xn, int xn_dtype,
+                   void* stream);
 int smoe_layernorm_rows(const float* x, int64_t row_stride, const float* gamma, const float* beta, float eps, int64_t T, int d,
                         float* out, void* stream);
 
@@ -555,6 +563,37 @@ int smoe_soft_ce_fwd(const void* logits, int dtype, const float* target, const i
                      float* row_loss, float* row_max, float* row_logsum, float* row_tsum, float* loss, void* stream);
 int smoe_soft_ce_bwd(const void* logits, int dtype, const float* target, const int64_t* labels, float smoothing, int64_t B, int C,
                      const float* row_max, const float* row_logsum, const float* row_tsum, const float* g, void* dlogits, void* stream);
+
+/* ---- knowledge distillation (main.py:688 `criterion = DistillationLoss(...)`; losses.py:53-72) -------------------------------------
+ * The distillation term between the student's distillation logits and a teacher's logits, both [B, C], each f32 / f16 / bf16 with its
+ * own dtype code, and its blend with the base loss.  mode 0 = soft, 1 = hard; tau > 0 (soft only); alpha.
+ * smoe_distill_fwd : soft: s = student / tau, t = teacher / tau; row_val[b] = sum_c p_t (log p_t - log p_s), p = softmax -- what
+ *                    F.kl_div(log_softmax(s), log_softmax(t), reduction='none', log_target=True).sum(1) gives; *distill_loss =
+ *                    (sum of row_val) * tau^2 / (B * C).  hard: row_val[b] = logsumexp(student[b]) - student[b, argmax_c teacher[b]]
+ *                    (F.cross_entropy against the teacher's argmax), *distill_loss = mean of row_val.  The argmax is torch.argmax's:
+ *                    the first maximal index, and a NaN counts as the maximum (the first NaN wins).
+ *                    *loss = *base_loss * (1 - alpha) + *distill_loss * alpha; base_loss is a DEVICE f32 scalar.
+ *                    row_val is f64 [B].  Also written, for the backward: row_stats f64 [4, B] = the student's row maximum (of the raw
+ *                    logits) and log of the sum of exp((x - max) / tau), the teacher's (soft; zeros in hard mode), and row_label i32 [B] =
+ *                    the argmax (hard; -1 in soft mode).  Both logit rows are read once (online max / sum; the soft term rides on the
+ *                    teacher's running maximum); the rows are summed in a fixed order: the same bits run to run.  Two launches.
+ *                    The arithmetic is double precision throughout (the soft term cancels when the student is close to the teacher):
+ *                    the two scalars and dlogits carry the f64 result's error (far below an f32 ulp) plus one rounding.
+ * smoe_distill_bwd : dlogits [B, C] in the student's dtype (rounded once from f32) = *g * alpha * tau / (B * C) * (p_s - p_t) (soft) or
+ *                    *g * alpha / B * (p_s - onehot(row_label)) (hard); g is a DEVICE f32 scalar (the gradient of the blended loss: it
+ *                    carries the loss scale).  The teacher gets no gradient; the base loss' gradient is *g * (1 - alpha), the caller's.
+ *                    B <= 65535.  One launch.
+ * Non-finite inputs: nothing is masked.  A NaN or +inf logit in either row, or a row of -inf, makes that row's value and (through a NaN
+ * log-sum) its whole gradient NaN; a -inf TEACHER logit makes the soft row value NaN (0 * -inf, as the reference's
+ * exp(log p_t) * (log p_t - log p_s) does); a -inf STUDENT logit under a finite teacher makes it +inf.  Other rows are untouched; the
+ * two scalars take the poison through the sum.  Which non-finite value appears (inf or NaN) is not preserved.
+ * 0 < C <= 2^30, B < 2^31 (forward).  16-byte accesses when C % 8 == 0 and student, teacher and dlogits are 16-byte aligned,
+ * element-wise otherwise.  B == 0 returns 0 at once; no allocation, no synchronisation, no atomics: both can be captured.          */
+int smoe_distill_fwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int mode, float tau, float alpha,
+                     const float* base_loss, int64_t B, int C, double* row_val, double* row_stats, int32_t* row_label,
+                     float* distill_loss, float* loss, void* stream);
+int smoe_distill_bwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int mode, float tau, float alpha, int64_t B,
+                     int C, const double* row_stats, const int32_t* row_label, const float* g, void* dlogits, void* stream);
 
 /* ---- small helpers ------------------------------------------------------------------------------------
  * elementwise cast between dtypes (weight shadow copies; not on the per-step path)                  */

@@ -111,6 +111,10 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "smoe_soft_ce_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "smoe_distill_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_void_p, c_int64, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "smoe_distill_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int64, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "smoe_unique_id_bytes": (c_int, []),
     "smoe_unique_id": (c_int, [c_void_p]),
     "smoe_ctx_create": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
@@ -126,6 +130,8 @@ SIGNATURES = {
     "smoe_patchify_cast": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "smoe_embed_ln": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_int, c_void_p,
                               c_void_p, c_int, c_void_p]),
+    "smoe_embed_ln2": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_int,
+                               c_void_p, c_void_p, c_int, c_void_p]),
     "smoe_layernorm_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p]),
     "smoe_skip_gate_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
                                    c_void_p, c_void_p]),

@@ -5,6 +5,8 @@
 //   smoe_embed_ln        x = cat(cls_token, tokens) + pos_embed (the f32 residual stream) AND LayerNorm(x) in 16 bit -- block 0's
 //                        norm1 -- in one pass over the projected tokens: the broadcast add, the class-token row and a whole
 //                        LayerNorm pass (154 MB read) become one kernel
+//   smoe_embed_ln2       the same with a second prefix row, the distillation token (DeiT's DistilledVisionTransformer,
+//                        models/model.py:48-67): x = cat(cls_token, dist_token, tokens) + pos_embed
 //   smoe_layernorm_rows  LayerNorm of rows that are row_stride elements apart (the class-token rows x[:, 0] in front of the head)
 #include "router16_kernel.h"
 
@@ -32,27 +34,29 @@ __global__ __launch_bounds__(256) void patchify_cast_kernel(const float* __restr
   }
 }
 
-// 16 lanes per token row (the router's layout): row (b, n) of the stream is tokens[b * P + n - 1] (n >= 1) or the class token
-// (n == 0), plus pos[n]; LayerNorm over it with the arithmetic of layernorm16_kernel / router16_kernel<LN>.
+// 16 lanes per token row (the router's layout): row (b, n) of the stream is tokens[b * P + n - NP] (n >= NP) or a prefix row (n == 0:
+// the class token; NP == 2, n == 1: the distillation token), plus pos[n]; LayerNorm over it with the arithmetic of layernorm16_kernel /
+// router16_kernel<LN>.  NP (1 or 2) is a template parameter: the NP == 1 code is what it was before there was a second prefix row.
 // (launch bounds: 3 waves per SIMD -- every load of a row is issued before the first use; gamma / beta are loaded behind the statistics
 //  (158 VGPRs at d = 768; with them hoisted the kernel needed 182 = 2 waves per SIMD, 96-100 us; now 89-92 us; 4 waves per SIMD = 128
 //  VGPRs, 5 spills: the same 90 us))
-template <typename TT, typename NT, int NJ>
+template <typename TT, typename NT, int NJ, int NP>
 __global__ __launch_bounds__(R16_THREADS, 3) void embed_ln_kernel(const TT* __restrict__ tok, const float* __restrict__ cls,
+                                                                  const float* __restrict__ dist,
                                                                   const float* __restrict__ pos, const float* __restrict__ g,
                                                                   const float* __restrict__ be, float eps, int64_t B, int P,
                                                                   float* __restrict__ x32, NT* __restrict__ xn) {
   constexpr int d = 64 * NJ;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = lane >> 4, u = lane & 15;
-  const int64_t T = B * (int64_t)(P + 1);
+  const int64_t T = B * (int64_t)(P + NP);
   const int64_t stride = (int64_t)gridDim.x * (R16_THREADS / 64) * 4;
   for (int64_t it0 = ((int64_t)blockIdx.x * (R16_THREADS / 64) + wave) * 4; it0 < T; it0 += stride) {
     const int64_t t = it0 + q;
     const bool live = t < T;
     const int64_t tc = live ? t : T - 1;
-    const int64_t b = tc / (P + 1);
-    const int n = (int)(tc - b * (P + 1));
+    const int64_t b = tc / (P + NP);
+    const int n = (int)(tc - b * (P + NP));
     f32x4 xv[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -60,9 +64,11 @@ __global__ __launch_bounds__(R16_THREADS, 3) void embed_ln_kernel(const TT* __re
       f32x4 v;
       if (n == 0) {
         v = *reinterpret_cast<const f32x4*>(cls + c);
+      } else if (NP == 2 && n == 1) {
+        v = *reinterpret_cast<const f32x4*>(dist + c);
       } else {
         float tmp[4];
-        load4(tok + (b * P + (n - 1)) * (int64_t)d + c, tmp);
+        load4(tok + (b * P + (n - NP)) * (int64_t)d + c, tmp);
         v = f32x4{tmp[0], tmp[1], tmp[2], tmp[3]};
       }
       xv[j] = v + *reinterpret_cast<const f32x4*>(pos + (int64_t)n * d + c);
@@ -104,18 +110,19 @@ __global__ __launch_bounds__(R16_THREADS, 3) void embed_ln_kernel(const TT* __re
 
 // The same pass with ONE WAVE PER ROW (d >= 768, where smoe_layernorm runs that layout: smoe_common.h smoe_ln_wave_layout) -- lane l
 // holds the elements [8 l + 512 i, +8) of its row; the LayerNorm is wave_row_stats, operation for operation smoe_layernorm's.
-template <typename TT, typename NT, int NI>
+template <typename TT, typename NT, int NI, int NP>
 __global__ __launch_bounds__(256) void embed_ln_wave_kernel(const TT* __restrict__ tok, const float* __restrict__ cls,
+                                                            const float* __restrict__ dist,
                                                             const float* __restrict__ pos, const float* __restrict__ g,
                                                             const float* __restrict__ be, float eps, int64_t B, int P, int d,
                                                             float* __restrict__ x32, NT* __restrict__ xn) {
   const int lane = threadIdx.x & 63;
   const int64_t wave_gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int64_t T = B * (int64_t)(P + 1);
+  const int64_t T = B * (int64_t)(P + NP);
   for (int64_t t = wave_gid; t < T; t += nwaves) {
-    const int64_t b = t / (P + 1);
-    const int n = (int)(t - b * (P + 1));
+    const int64_t b = t / (P + NP);
+    const int n = (int)(t - b * (P + NP));
     float v[NI][8];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -123,7 +130,8 @@ __global__ __launch_bounds__(256) void embed_ln_wave_kernel(const TT* __restrict
       if (c < d) {
         float a[8], pe[8];
         if (n == 0) load8(cls + c, a);
-        else load8(tok + (b * P + (n - 1)) * (int64_t)d + c, a);
+        else if (NP == 2 && n == 1) load8(dist + c, a);
+        else load8(tok + (b * P + (n - NP)) * (int64_t)d + c, a);
         load8(pos + (int64_t)n * d + c, pe);
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[i][q] = a[q] + pe[q];
@@ -278,29 +286,36 @@ extern "C" int smoe_patchify_cast(const float* images, int64_t B, int C, int H, 
   return 0;
 }
 
-extern "C" int smoe_embed_ln(const void* tokens, int tok_dtype, const float* cls_token, const float* pos_embed, const float* ln_gamma,
-                             const float* ln_beta, float ln_eps, int64_t B, int P, int d, float* x32, void* xn, int xn_dtype,
-                             void* stream) {
-  SMOE_REQUIRE(B >= 0 && P >= 1 && (d == 192 || d == 384 || d == 768 || d == 1024), "smoe_embed_ln: unsupported shape B=%lld P=%d d=%d",
+namespace {
+// smoe_embed_ln (dist_token == NULL: one prefix row) and smoe_embed_ln2 (two): the same checks, layouts and grids
+int embed_ln_launch(const char* fn, const void* tokens, int tok_dtype, const float* cls_token, const float* dist_token,
+                    const float* pos_embed, const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t B, int P, int d, float* x32,
+                    void* xn, int xn_dtype, void* stream) {
+  SMOE_REQUIRE(B >= 0 && P >= 1 && (d == 192 || d == 384 || d == 768 || d == 1024), "%s: unsupported shape B=%lld P=%d d=%d", fn,
                (long long)B, P, d);
   if (B == 0) return 0;
-  SMOE_REQUIRE(tokens && cls_token && pos_embed && x32, "smoe_embed_ln: null pointer");
-  SMOE_REQUIRE(tok_dtype == SMOE_F16 || tok_dtype == SMOE_BF16, "smoe_embed_ln: tokens must be f16 or bf16");
-  SMOE_REQUIRE(!xn || xn_dtype == SMOE_F16 || xn_dtype == SMOE_BF16, "smoe_embed_ln: xn must be f16 or bf16");
+  SMOE_REQUIRE(tokens && cls_token && pos_embed && x32, "%s: null pointer", fn);
+  SMOE_REQUIRE(tok_dtype == SMOE_F16 || tok_dtype == SMOE_BF16, "%s: tokens must be f16 or bf16", fn);
+  SMOE_REQUIRE(!xn || xn_dtype == SMOE_F16 || xn_dtype == SMOE_BF16, "%s: xn must be f16 or bf16", fn);
   hipStream_t s = (hipStream_t)stream;
+  const int np = dist_token ? 2 : 1;
+  const int64_t rows = B * (int64_t)(P + np);
   if (smoe_ln_wave_layout(d) && d > 512 && d <= 1024 && d % 8 == 0) {   // the layout smoe_layernorm uses at this width: the same bits
-    const int64_t rows = B * (int64_t)(P + 1), blocks = (rows + 3) / 4;
+    const int64_t blocks = (rows + 3) / 4;
     const int wg = (int)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks));
     const bool xb = xn && xn_dtype == SMOE_BF16;
-#define ELW(TT, NT) hipLaunchKernelGGL((embed_ln_wave_kernel<TT, NT, 2>), dim3(wg), dim3(256), 0, s, (const TT*)tokens, cls_token, pos_embed, ln_gamma, ln_beta, ln_eps, B, P, d, x32, (NT*)xn)
+#define ELW1(TT, NT, NP) hipLaunchKernelGGL((embed_ln_wave_kernel<TT, NT, 2, NP>), dim3(wg), dim3(256), 0, s, (const TT*)tokens, cls_token, dist_token, pos_embed, ln_gamma, ln_beta, ln_eps, B, P, d, x32, (NT*)xn)
+#define ELW(TT, NT) do { if (np == 2) ELW1(TT, NT, 2); else ELW1(TT, NT, 1); } while (0)
     if (tok_dtype == SMOE_F16) { if (xb) ELW(f16, bf16_bits); else ELW(f16, f16); }
     else { if (xb) ELW(bf16_bits, bf16_bits); else ELW(bf16_bits, f16); }
 #undef ELW
-    SMOE_CHECK_LAUNCH("smoe_embed_ln/wave");
+#undef ELW1
+    SMOE_CHECK_LAUNCH(np == 2 ? "smoe_embed_ln2/wave" : "smoe_embed_ln/wave");
     return 0;
   }
-  const int grid = rows_grid16(B * (int64_t)(P + 1));
-#define EL(TT, NT, NJ) hipLaunchKernelGGL((embed_ln_kernel<TT, NT, NJ>), dim3(grid), dim3(R16_THREADS), 0, s, (const TT*)tokens, cls_token, pos_embed, ln_gamma, ln_beta, ln_eps, B, P, x32, (NT*)xn)
+  const int grid = rows_grid16(rows);
+#define EL1(TT, NT, NJ, NP) hipLaunchKernelGGL((embed_ln_kernel<TT, NT, NJ, NP>), dim3(grid), dim3(R16_THREADS), 0, s, (const TT*)tokens, cls_token, dist_token, pos_embed, ln_gamma, ln_beta, ln_eps, B, P, x32, (NT*)xn)
+#define EL(TT, NT, NJ) do { if (np == 2) EL1(TT, NT, NJ, 2); else EL1(TT, NT, NJ, 1); } while (0)
 #define EL_D(TT, NT)                                                  \
   switch (d) {                                                        \
     case 192: EL(TT, NT, 3); break;                                   \
@@ -313,8 +328,25 @@ extern "C" int smoe_embed_ln(const void* tokens, int tok_dtype, const float* cls
   else { if (xbf) { EL_D(bf16_bits, bf16_bits) } else { EL_D(bf16_bits, f16) } }
 #undef EL_D
 #undef EL
-  SMOE_CHECK_LAUNCH("smoe_embed_ln");
+#undef EL1
+  SMOE_CHECK_LAUNCH(np == 2 ? "smoe_embed_ln2" : "smoe_embed_ln");
   return 0;
+}
+}  // namespace
+
+extern "C" int smoe_embed_ln(const void* tokens, int tok_dtype, const float* cls_token, const float* pos_embed, const float* ln_gamma,
+                             const float* ln_beta, float ln_eps, int64_t B, int P, int d, float* x32, void* xn, int xn_dtype,
+                             void* stream) {
+  return embed_ln_launch("smoe_embed_ln", tokens, tok_dtype, cls_token, nullptr, pos_embed, ln_gamma, ln_beta, ln_eps, B, P, d, x32, xn,
+                         xn_dtype, stream);
+}
+
+// dist_token == NULL: one prefix row, the launch smoe_embed_ln makes
+extern "C" int smoe_embed_ln2(const void* tokens, int tok_dtype, const float* cls_token, const float* dist_token, const float* pos_embed,
+                              const float* ln_gamma, const float* ln_beta, float ln_eps, int64_t B, int P, int d, float* x32, void* xn,
+                              int xn_dtype, void* stream) {
+  return embed_ln_launch("smoe_embed_ln2", tokens, tok_dtype, cls_token, dist_token, pos_embed, ln_gamma, ln_beta, ln_eps, B, P, d, x32,
+                         xn, xn_dtype, stream);
 }
 
 extern "C" int smoe_layernorm_rows(const float* x, int64_t row_stride, const float* gamma, const float* beta, float eps, int64_t T,

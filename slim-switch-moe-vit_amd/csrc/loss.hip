@@ -7,6 +7,10 @@
 //   smoe_soft_ce_fwd  : mean over rows of sum(-t * log_softmax(x)) for dense targets, or of the label-smoothing loss for integer
 //                       labels; one online max / sum pass per row + a fixed-order sum of the row losses (deterministic)
 //   smoe_soft_ce_bwd  : dlogits = g (softmax(x) sum(t) - t) / B in the logits' dtype, g a device scalar (it carries the loss scale)
+// and the criterion every run of the reference ends in (main.py:688 DistillationLoss; losses.py:53-72):
+//   smoe_distill_fwd  : the distillation term between the student's distillation logits and a teacher's logits -- soft: KL(teacher ||
+//                       student) at temperature tau; hard: cross-entropy against the teacher's argmax -- and its blend with the base loss
+//   smoe_distill_bwd  : its gradient for the student's distillation logits (the teacher gets none)
 #include "smoe_common.h"
 #include <type_traits>
 
@@ -320,6 +324,253 @@ bool ce_vec_ok(const void* logits, const void* target, const void* dlogits, int 
 
 constexpr int GRID_Y_MAX = 65535;
 
+// ---- distillation (losses.py:53-72) -----------------------------------------------------------------------------------------
+// The row kernels compute in DOUBLE (MaxSumD / distill_step are MaxSum / ce_step with a double sum): the soft term is a difference of
+// nearly equal sums when the student is close to the teacher, and an f32 emulation of its online form on the CPU came out at up to
+// 1.8 x the error bar the tests take from torch's own f32 composition (at B = 2 rows, where that bar rests on two samples).  In double
+// the arithmetic error is far below one f32 ulp, so what is stored is, to that accuracy, the f64 result rounded to the output type.
+// Cost on the GPU: profiles/r10_distillation.md.
+constexpr int DISTILL_SOFT = 0, DISTILL_HARD = 1;
+
+// torch.argmax's order: a takes b's place when it is NaN and b is not, when it is greater, or when it ties (two NaNs tie) at a lower index
+__device__ __forceinline__ bool argmax_takes(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > bv || (v == bv && i < bi);
+}
+
+// running (max of the raw logits, sum of exp((x - max) / tau)) of a row, the sum in double; MaxSum's rules for non-finite logits: the
+// maximum is never NaN, a NaN logit lives on in the sum, a -inf logit adds 0, +inf - +inf = NaN poisons the sum
+struct MaxSumD {
+  float m;
+  double s;
+  __device__ __forceinline__ double factor(float mm, double itau) const { return m == mm ? 1.0 : exp(((double)m - (double)mm) * itau); }
+};
+
+// K logits of a thread: ce_step in double.  acc (teacher rows only, with the student's logits in sv): sum of exp((t - max) / tau)
+// (t - s) / tau, rescaled with the sum whenever the maximum moves.  Nothing is masked there: a -inf teacher logit gives 0 * -inf = NaN,
+// as the reference's exp(log p_t) * (log p_t - log p_s) does.
+template <bool KL>
+__device__ __forceinline__ void distill_step(MaxSumD& ms, double& acc, const float (&v)[CE_K], const float (&sv)[CE_K],
+                                             const bool (&ok)[CE_K], double itau) {
+  const float ninf = -__builtin_inff();
+  float vm = ninf;
+#pragma unroll
+  for (int q = 0; q < CE_K; ++q) vm = fmaxf(vm, ok[q] ? v[q] : ninf);
+  if (vm > ms.m) {
+    const double f = exp(((double)ms.m - (double)vm) * itau);      // (ms.m == -inf: the sums are 0 or NaN, and stay that)
+    ms.s *= f;
+    if (KL) acc *= f;
+    ms.m = vm;
+  }
+#pragma unroll
+  for (int q = 0; q < CE_K; ++q) {
+    if (!ok[q]) continue;
+    const double e = exp(((double)v[q] - (double)ms.m) * itau);
+    ms.s += v[q] == ninf ? 0.0 : e;
+    if (KL) acc += e * (((double)v[q] - (double)sv[q]) * itau);
+  }
+}
+
+// One workgroup per row, both logit rows read once.  soft: s = student / tau, t = teacher / tau, row value = sum p_t (log p_t - log p_s)
+// = acc / S_t - (m_t - m_s) / tau - (log S_t - log S_s) with (m, S) the online max / sum of each row.  hard: row value =
+// logsumexp(student) - student[argmax teacher], the argmax found in the same pass.  stats f64 [4, B]: the student's maximum (raw) and
+// log-sum, the teacher's (soft); a log-sum is stored as NaN when its log-sum-exp is not finite (the backward then poisons the row, as
+// the reference's log_softmax does).  label [B]: the argmax (hard), -1 (soft).
+template <typename TS, typename TT, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void distill_fwd_kernel(const TS* __restrict__ student, const TT* __restrict__ teacher, int mode,
+                                                                   float tau, int B, int C, double* __restrict__ row_val,
+                                                                   double* __restrict__ stats, int32_t* __restrict__ label) {
+  constexpr int NW = LOSS_THREADS / 64;
+  __shared__ double redd[3][NW];
+  __shared__ float redf[3][NW];
+  __shared__ int redi[NW];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const TS* __restrict__ x = student + (size_t)row * C;
+  const TT* __restrict__ y = teacher + (size_t)row * C;
+  const bool hard = mode == DISTILL_HARD;
+  const double itau = hard ? 1.0 : 1.0 / (double)tau;
+  const float ninf = -__builtin_inff();
+  MaxSumD ms{ninf, 0.0}, mt{ninf, 0.0};
+  double acc = 0.0;
+  float bv = ninf;
+  int bi = 0x7fffffff;
+  const int span = LOSS_THREADS * CE_K;
+  for (int c0 = 0; c0 < C; c0 += span) {
+    float sv[CE_K], tv[CE_K];
+    bool ok[CE_K];
+    // both paths give a thread the same 8 consecutive logits, so the element path (any C, any alignment) computes the vector path's bits
+    const int c = c0 + tid * CE_K;
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) { ok[q] = c + q < C; sv[q] = 0.f; tv[q] = 0.f; }
+    if constexpr (VEC) {     // C % 8 == 0 and 16-byte aligned bases
+      if (c < C) { load8(x + c, sv); load8(y + c, tv); }
+    } else {
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q)
+        if (ok[q]) { sv[q] = to_f32<TS>(x[c + q]); tv[q] = to_f32<TT>(y[c + q]); }
+    }
+    distill_step<false>(ms, acc, sv, sv, ok, itau);
+    if (hard) {
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q)
+        if (ok[q] && argmax_takes(tv[q], c + q, bv, bi)) { bv = tv[q]; bi = c + q; }
+    } else {
+      distill_step<true>(mt, acc, tv, sv, ok, itau);
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    {
+      const float m2 = __shfl_xor(ms.m, m, 64);
+      const double s2 = __shfl_xor(ms.s, m, 64);
+      const float mm = fmaxf(ms.m, m2);
+      ms.s = ms.s * ms.factor(mm, itau) + s2 * MaxSumD{m2, 0.0}.factor(mm, itau);
+      ms.m = mm;
+    }
+    if (hard) {
+      const float v2 = __shfl_xor(bv, m, 64);
+      const int i2 = __shfl_xor(bi, m, 64);
+      if (argmax_takes(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+    } else {
+      const float m2 = __shfl_xor(mt.m, m, 64);
+      const double s2 = __shfl_xor(mt.s, m, 64), a2 = __shfl_xor(acc, m, 64);
+      const float mm = fmaxf(mt.m, m2);
+      const double f1 = mt.factor(mm, itau), f2 = MaxSumD{m2, 0.0}.factor(mm, itau);
+      mt.s = mt.s * f1 + s2 * f2;
+      acc = acc * f1 + a2 * f2;
+      mt.m = mm;
+    }
+  }
+  const int w = tid >> 6;
+  if ((tid & 63) == 0) {
+    redf[0][w] = ms.m; redd[0][w] = ms.s; redf[1][w] = mt.m; redd[1][w] = mt.s; redd[2][w] = acc; redf[2][w] = bv; redi[w] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    MaxSumD a{redf[0][0], redd[0][0]}, t{redf[1][0], redd[1][0]};
+    acc = redd[2][0]; bv = redf[2][0]; bi = redi[0];
+    for (int k = 1; k < NW; ++k) {
+      const float mm = fmaxf(a.m, redf[0][k]);
+      a.s = a.s * a.factor(mm, itau) + redd[0][k] * MaxSumD{redf[0][k], 0.0}.factor(mm, itau);
+      a.m = mm;
+      if (hard) {
+        if (argmax_takes(redf[2][k], redi[k], bv, bi)) { bv = redf[2][k]; bi = redi[k]; }
+      } else {
+        const float tm = fmaxf(t.m, redf[1][k]);
+        const double f1 = t.factor(tm, itau), f2 = MaxSumD{redf[1][k], 0.0}.factor(tm, itau);
+        t.s = t.s * f1 + redd[1][k] * f2;
+        acc = acc * f1 + redd[2][k] * f2;
+        t.m = tm;
+      }
+    }
+    const double nan = __builtin_nan("");
+    double ls = log(a.s), lt = 0.0, tm = 0.0, val;
+    if (!(fabs((double)a.m * itau + ls) <= 1.7e308)) ls = nan;
+    if (hard) {
+      val = ((double)a.m + ls) - (double)to_f32<TS>(x[bi]);       // (C >= 1: bi is an index of the row)
+    } else {
+      lt = log(t.s);
+      tm = (double)t.m;
+      val = acc / t.s - ((double)t.m - (double)a.m) * itau - (lt - ls);
+      if (!(fabs(tm * itau + lt) <= 1.7e308)) lt = nan;
+    }
+    row_val[row] = val;
+    stats[row] = (double)a.m;
+    stats[(size_t)B + row] = ls;
+    stats[2 * (size_t)B + row] = tm;
+    stats[3 * (size_t)B + row] = lt;
+    label[row] = hard ? bi : -1;
+  }
+}
+
+// *distill = (sum of the row values in a fixed order) * tau^2 / (B C) (soft) or / B (hard); *loss = base (1 - alpha) + distill alpha;
+// in double, each rounded to f32 at the store
+__global__ __launch_bounds__(LOSS_THREADS) void distill_blend_kernel(const double* __restrict__ row_val, int B, int C, int mode, float tau,
+                                                                     float alpha, const float* __restrict__ base,
+                                                                     float* __restrict__ distill, float* __restrict__ loss) {
+  __shared__ double red[LOSS_THREADS / 64];
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < B; r += LOSS_THREADS) acc += row_val[r];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sum = (red[0] + red[1]) + (red[2] + red[3]);
+    const double d = mode == DISTILL_HARD ? sum / (double)B : sum * ((double)tau * (double)tau) / ((double)B * (double)C);
+    *distill = (float)d;
+    *loss = (float)((double)*base * (1.0 - (double)alpha) + d * (double)alpha);
+  }
+}
+
+// soft: dlogits = g alpha tau / (B C) (p_s - p_t);  hard: g alpha / B (p_s - onehot(label)).  p = exp((x - max) / tau - logsum), in double
+template <typename TS, typename TT, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void distill_bwd_kernel(const TS* __restrict__ student, const TT* __restrict__ teacher, int mode,
+                                                                   float tau, float alpha, int B, int C, const double* __restrict__ stats,
+                                                                   const int32_t* __restrict__ label, const float* __restrict__ g,
+                                                                   TS* __restrict__ dlogits) {
+  const int row = blockIdx.y;
+  const size_t at = (size_t)row * C;
+  const bool hard = mode == DISTILL_HARD;
+  const double itau = hard ? 1.0 : 1.0 / (double)tau;
+  const double ms = stats[row], ls = stats[(size_t)B + row], mt = stats[2 * (size_t)B + row], lt = stats[3 * (size_t)B + row];
+  const double scale = hard ? (double)*g * (double)alpha / (double)B
+                            : (double)*g * (double)alpha * (double)tau / ((double)B * (double)C);
+  const int lab = hard ? label[row] : -1;
+  if constexpr (VEC) {
+    const int c = (blockIdx.x * LOSS_THREADS + threadIdx.x) * CE_K;
+    if (c >= C) return;
+    float sv[CE_K], tv[CE_K], o[CE_K];
+    load8(student + at + c, sv);
+    if (!hard) load8(teacher + at + c, tv);
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      const double ps = exp(((double)sv[q] - ms) * itau - ls);
+      const double sub = hard ? (c + q == lab ? 1.0 : 0.0) : exp(((double)tv[q] - mt) * itau - lt);
+      o[q] = (float)((ps - sub) * scale);
+    }
+    store8(dlogits + at + c, o);
+  } else {
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      const int c = blockIdx.x * (LOSS_THREADS * CE_K) + q * LOSS_THREADS + threadIdx.x;
+      if (c >= C) continue;
+      const double ps = exp(((double)to_f32<TS>(student[at + c]) - ms) * itau - ls);
+      const double sub = hard ? (c == lab ? 1.0 : 0.0) : exp(((double)to_f32<TT>(teacher[at + c]) - mt) * itau - lt);
+      dlogits[at + c] = from_f32<TS>((float)((ps - sub) * scale));
+    }
+  }
+}
+
+template <typename TS, typename TT>
+void launch_distill_fwd(bool vec, hipStream_t s, const void* student, const void* teacher, int mode, float tau, int B, int C, double* row_val,
+                        double* stats, int32_t* label) {
+  if (vec) hipLaunchKernelGGL((distill_fwd_kernel<TS, TT, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, B, C, row_val, stats, label);
+  else hipLaunchKernelGGL((distill_fwd_kernel<TS, TT, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, B, C, row_val, stats, label);
+}
+
+template <typename TS, typename TT>
+void launch_distill_bwd(bool vec, dim3 grid, hipStream_t s, const void* student, const void* teacher, int mode, float tau, float alpha, int B,
+                        int C, const double* stats, const int32_t* label, const float* g, void* dlogits) {
+  if (vec) hipLaunchKernelGGL((distill_bwd_kernel<TS, TT, true>), grid, dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, alpha, B, C, stats, label, g, (TS*)dlogits);
+  else hipLaunchKernelGGL((distill_bwd_kernel<TS, TT, false>), grid, dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, alpha, B, C, stats, label, g, (TS*)dlogits);
+}
+
+// the nine (student, teacher) dtype pairs
+#define DISTILL_PAIRS(CALL)                                                                          \
+  switch (s_dtype * 3 + t_dtype) {                                                                  \
+    case SMOE_F32 * 3 + SMOE_F32: CALL(float, float); break;                                        \
+    case SMOE_F32 * 3 + SMOE_F16: CALL(float, f16); break;                                          \
+    case SMOE_F32 * 3 + SMOE_BF16: CALL(float, bf16_bits); break;                                   \
+    case SMOE_F16 * 3 + SMOE_F32: CALL(f16, float); break;                                          \
+    case SMOE_F16 * 3 + SMOE_F16: CALL(f16, f16); break;                                            \
+    case SMOE_F16 * 3 + SMOE_BF16: CALL(f16, bf16_bits); break;                                     \
+    case SMOE_BF16 * 3 + SMOE_F32: CALL(bf16_bits, float); break;                                   \
+    case SMOE_BF16 * 3 + SMOE_F16: CALL(bf16_bits, f16); break;                                     \
+    default: CALL(bf16_bits, bf16_bits); break;                                                     \
+  }
+
 }  // namespace
 
 extern "C" int smoe_mixup_images(float* x, int64_t B, int C, int H, int W, const float* lam, const float* one_minus,
@@ -389,5 +640,44 @@ extern "C" int smoe_soft_ce_bwd(const void* logits, int dtype, const float* targ
     default: launch_ce_bwd<bf16_bits>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
   }
   SMOE_CHECK_LAUNCH("smoe_soft_ce_bwd");
+  return 0;
+}
+
+extern "C" int smoe_distill_fwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int mode, float tau, float alpha,
+                                const float* base_loss, int64_t B, int C, double* row_val, double* row_stats, int32_t* row_label,
+                                float* distill_loss, float* loss, void* stream) {
+  SMOE_REQUIRE(B >= 0 && B < (1ll << 31) && C > 0 && C <= (1 << 30), "smoe_distill_fwd: bad sizes (B < 2^31, 0 < C <= 2^30)");
+  SMOE_REQUIRE(smoe_dtype_ok(s_dtype) && smoe_dtype_ok(t_dtype), "smoe_distill_fwd: bad dtype code (student %d, teacher %d)", s_dtype, t_dtype);
+  SMOE_REQUIRE(mode == DISTILL_SOFT || mode == DISTILL_HARD, "smoe_distill_fwd: bad mode %d (0 = soft, 1 = hard)", mode);
+  SMOE_REQUIRE(tau > 0.f, "smoe_distill_fwd: tau must be positive (got %g)", (double)tau);
+  if (B == 0) return 0;
+  SMOE_REQUIRE(student && teacher && base_loss && row_val && row_stats && row_label && distill_loss && loss, "smoe_distill_fwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(student, teacher, nullptr, C);
+#define DF(TS, TT) launch_distill_fwd<TS, TT>(vec, s, student, teacher, mode, tau, (int)B, C, row_val, row_stats, row_label)
+  DISTILL_PAIRS(DF)
+#undef DF
+  SMOE_CHECK_LAUNCH("smoe_distill_fwd");
+  hipLaunchKernelGGL(distill_blend_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_val, (int)B, C, mode, tau, alpha, base_loss, distill_loss, loss);
+  SMOE_CHECK_LAUNCH("smoe_distill_fwd (blend)");
+  return 0;
+}
+
+extern "C" int smoe_distill_bwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int mode, float tau, float alpha,
+                                int64_t B, int C, const double* row_stats, const int32_t* row_label, const float* g, void* dlogits,
+                                void* stream) {
+  SMOE_REQUIRE(B >= 0 && B <= GRID_Y_MAX && C > 0 && C <= (1 << 30), "smoe_distill_bwd: bad sizes (B <= 65535, 0 < C <= 2^30)");
+  SMOE_REQUIRE(smoe_dtype_ok(s_dtype) && smoe_dtype_ok(t_dtype), "smoe_distill_bwd: bad dtype code (student %d, teacher %d)", s_dtype, t_dtype);
+  SMOE_REQUIRE(mode == DISTILL_SOFT || mode == DISTILL_HARD, "smoe_distill_bwd: bad mode %d (0 = soft, 1 = hard)", mode);
+  SMOE_REQUIRE(tau > 0.f, "smoe_distill_bwd: tau must be positive (got %g)", (double)tau);
+  if (B == 0) return 0;
+  SMOE_REQUIRE(student && teacher && row_stats && row_label && g && dlogits, "smoe_distill_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(student, teacher, dlogits, C);
+  const dim3 grid((unsigned)((C + LOSS_THREADS * CE_K - 1) / (LOSS_THREADS * CE_K)), (unsigned)B);
+#define DB(TS, TT) launch_distill_bwd<TS, TT>(vec, grid, s, student, teacher, mode, tau, alpha, (int)B, C, row_stats, row_label, g, dlogits)
+  DISTILL_PAIRS(DB)
+#undef DB
+  SMOE_CHECK_LAUNCH("smoe_distill_bwd");
   return 0;
 }

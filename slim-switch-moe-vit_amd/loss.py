@@ -8,6 +8,12 @@ about ten small launches inside a step whose kernels are all small (profiles/r05
 host sync, capturable (engine.GraphedTrainStep).  Under autocast the 16-bit logits are taken as they are (the kernels compute in
 f32); the loss is an f32 scalar.  Anything else (CPU tensors, other dtypes or layouts, targets that need a gradient) takes timm's
 torch lines.
+
+``DistillationLoss`` is the reference's ``losses.py`` (main.py:688: every run's criterion is one, ``--distillation-type none`` included): the base
+criterion on the class-token logits, blended with a distillation term between the distillation-token logits and a teacher's.  CUDA
+logits go through one ``torch.autograd.Function`` over ``smoe_distill_fwd`` / ``smoe_distill_bwd`` -- two launches forward, one backward
+(upstream: two log-softmaxes, two divisions, kl_div, sum, two scalings and the blend, and their backward); everything else takes the
+reference's torch lines.
 """
 from __future__ import annotations
 
@@ -82,3 +88,70 @@ class LabelSmoothingCrossEntropy(nn.Module):
         smooth_loss = -logprobs.mean(dim=-1)
         loss = self.confidence * nll_loss + self.smoothing * smooth_loss
         return loss.mean()
+
+
+class _Distill(torch.autograd.Function):
+    """``base * (1 - alpha) + distill(student, teacher) * alpha`` (losses.py:53-72) on smoe_distill_fwd / smoe_distill_bwd."""
+
+    @staticmethod
+    def forward(ctx, base_loss, student, teacher, mode: str, tau: float, alpha: float):
+        loss, _, _, stats, labels = ops.distill_fwd(student, teacher, base_loss.detach().reshape(()), mode, tau, alpha)
+        ctx.save_for_backward(student, teacher, stats, labels)
+        ctx.mode, ctx.tau, ctx.alpha = mode, tau, alpha
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        student, teacher, stats, labels = ctx.saved_tensors
+        if g.dtype != torch.float32:
+            g = g.float()
+        g = g.contiguous()
+        dx = ops.distill_bwd(student, teacher, stats, labels, g, ctx.mode, ctx.tau, ctx.alpha) if ctx.needs_input_grad[1] else None
+        return (g * (1 - ctx.alpha) if ctx.needs_input_grad[0] else None), dx, None, None, None, None
+
+
+class DistillationLoss(nn.Module):
+    """The reference's ``losses.DistillationLoss``: wraps a standard criterion and adds a knowledge-distillation loss that takes a
+    teacher model's prediction as additional supervision.  ``forward(inputs, outputs, labels)``: ``inputs`` go to the teacher,
+    ``outputs`` is the student's ``(class-token logits, distillation-token logits)`` pair (DistilledVisionTransformer in training
+    mode), ``labels`` go to the base criterion.  ``soft``: KL(teacher || student) at temperature ``tau``, summed, times
+    ``tau^2 / numel``; ``hard``: cross-entropy against the teacher's argmax; the result is ``base * (1 - alpha) + distill * alpha``."""
+
+    def __init__(self, base_criterion: nn.Module, teacher_model: nn.Module, distillation_type: str, alpha: float, tau: float):
+        super().__init__()
+        self.base_criterion = base_criterion
+        self.teacher_model = teacher_model
+        assert distillation_type in ['none', 'soft', 'hard']
+        self.distillation_type = distillation_type
+        self.alpha = alpha
+        self.tau = tau
+
+    def forward(self, inputs, outputs, labels):
+        outputs_kd = None
+        if not isinstance(outputs, torch.Tensor):
+            outputs, outputs_kd = outputs       # the model returns (outputs, outputs_kd)
+        base_loss = self.base_criterion(outputs, labels)
+        if self.distillation_type == 'none':
+            return base_loss
+        if outputs_kd is None:
+            raise ValueError("When knowledge distillation is enabled, the model is "
+                             "expected to return a Tuple[Tensor, Tensor] with the output of the "
+                             "class_token and the dist_token")
+        with torch.no_grad():                   # no backpropagation through the teacher
+            teacher_outputs = self.teacher_model(inputs)
+        if self._kernel_ok(base_loss, outputs_kd, teacher_outputs):
+            return _Distill.apply(base_loss if base_loss.dtype == torch.float32 else base_loss.float(), outputs_kd, teacher_outputs,
+                                  self.distillation_type, float(self.tau), float(self.alpha))
+        if self.distillation_type == 'soft':
+            T = self.tau
+            distillation_loss = F.kl_div(F.log_softmax(outputs_kd / T, dim=1), F.log_softmax(teacher_outputs / T, dim=1),
+                                         reduction='sum', log_target=True) * (T * T) / outputs_kd.numel()
+        else:
+            distillation_loss = F.cross_entropy(outputs_kd, teacher_outputs.argmax(dim=1))
+        return base_loss * (1 - self.alpha) + distillation_loss * self.alpha
+
+    def _kernel_ok(self, base_loss, kd, teacher) -> bool:
+        return (isinstance(teacher, torch.Tensor) and isinstance(base_loss, torch.Tensor) and _logits_ok(kd) and kd.dim() == 2
+                and _logits_ok(teacher) and teacher.shape == kd.shape and teacher.device == kd.device and not teacher.requires_grad
+                and base_loss.dim() == 0 and base_loss.device == kd.device and base_loss.is_floating_point()
+                and isinstance(self.tau, (int, float)) and self.tau > 0 and isinstance(self.alpha, (int, float)))

@@ -216,33 +216,52 @@ def patchify_cast(images: torch.Tensor, ph: int, pw: int, out_dtype: torch.dtype
 
 
 def embed_ln(tokens: torch.Tensor, cls_token: torch.Tensor, pos_embed: torch.Tensor, B: int, P: int,
-             ln: Optional[tuple] = None, xn_dtype: torch.dtype = torch.float16):
+             ln: Optional[tuple] = None, xn_dtype: torch.dtype = torch.float16, dist_token: Optional[torch.Tensor] = None):
     """(x32 [B, P + 1, d], xn | None): the f32 stream cat(cls, tokens) + pos_embed and, with ``ln`` = (weight, bias, eps), its
-    LayerNorm in 16 bit from the same pass (smoe_embed_ln)."""
+    LayerNorm in 16 bit from the same pass (smoe_embed_ln).  With ``dist_token`` the stream is cat(cls, dist, tokens) + pos_embed,
+    [B, P + 2, d] (smoe_embed_ln2)."""
     _chk(tokens, "tokens", ndim=2)
     d = tokens.shape[1]
     cls = cls_token.detach().reshape(-1)
     pos = pos_embed.detach().reshape(-1, d)
     _chk(cls, "cls_token", torch.float32, 1)
     _chk(pos, "pos_embed", torch.float32, 2)
-    if cls.numel() != d or pos.shape[0] != P + 1 or tokens.shape[0] != B * P:
+    npre = 1
+    dist = None
+    if dist_token is not None:
+        dist = dist_token.detach().reshape(-1)
+        _chk(dist, "dist_token", torch.float32, 1)
+        npre = 2
+        if dist.numel() != d or dist.device != tokens.device:
+            raise RuntimeError("embed_ln: shapes disagree")
+    if cls.numel() != d or pos.shape[0] != P + npre or tokens.shape[0] != B * P:
         raise RuntimeError("embed_ln: shapes disagree")
-    x32 = torch.empty((B, P + 1, d), dtype=torch.float32, device=tokens.device)
-    xn = torch.empty((B, P + 1, d), dtype=xn_dtype, device=tokens.device) if ln is not None else None
+    x32 = torch.empty((B, P + npre, d), dtype=torch.float32, device=tokens.device)
+    xn = torch.empty((B, P + npre, d), dtype=xn_dtype, device=tokens.device) if ln is not None else None
     lg, lb, eps = ln if ln is not None else (None, None, 0.0)
-    with _timed("embed_ln", {"bytes": B * (P + 1) * d * (2 + 4 + (2 if ln is not None else 0))}, tokens):
-        rc = _lib.load().smoe_embed_ln(_ptr(tokens), dtype_code(tokens.dtype), _ptr(cls), _ptr(pos), _ptr(lg), _ptr(lb), float(eps), B, P, d,
-                                       _ptr(x32), _ptr(xn), dtype_code(xn_dtype), _stream(tokens))
-    _lib.check(rc, "smoe_embed_ln")
+    with _timed("embed_ln", {"bytes": B * (P + npre) * d * (2 + 4 + (2 if ln is not None else 0))}, tokens):
+        if dist is None:
+            rc = _lib.load().smoe_embed_ln(_ptr(tokens), dtype_code(tokens.dtype), _ptr(cls), _ptr(pos), _ptr(lg), _ptr(lb), float(eps), B, P, d,
+                                           _ptr(x32), _ptr(xn), dtype_code(xn_dtype), _stream(tokens))
+        else:
+            rc = _lib.load().smoe_embed_ln2(_ptr(tokens), dtype_code(tokens.dtype), _ptr(cls), _ptr(dist), _ptr(pos), _ptr(lg), _ptr(lb),
+                                            float(eps), B, P, d, _ptr(x32), _ptr(xn), dtype_code(xn_dtype), _stream(tokens))
+    _lib.check(rc, "smoe_embed_ln" if dist is None else "smoe_embed_ln2")
     return x32, xn
 
 
 def layernorm_rows(x: torch.Tensor, row_stride: int, T: int, d: int, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
-                   eps: float) -> torch.Tensor:
-    """LayerNorm of the T rows x.data_ptr() + t * row_stride (f32, d elements each) -> f32 [T, d] (smoe_layernorm_rows)."""
+                   eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm of the T rows x.data_ptr() + t * row_stride (f32, d elements each) -> f32 [T, d] (smoe_layernorm_rows); ``out``:
+    a contiguous f32 [T, d] to write instead of a new tensor."""
     if not (x.is_cuda and x.dtype == torch.float32):
         raise RuntimeError("layernorm_rows: f32 GPU tensor expected")
-    out = torch.empty((T, d), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((T, d), dtype=torch.float32, device=x.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (T, d) and out.device == x.device):
+        raise RuntimeError("layernorm_rows: out must be a contiguous f32 [T, d] on x's device")
+    if x.numel() < (T - 1) * int(row_stride) + d:
+        raise RuntimeError("layernorm_rows: the last row ends outside x")
     rc = _lib.load().smoe_layernorm_rows(_ptr(x), int(row_stride), _ptr(weight), _ptr(bias), float(eps), T, d, _ptr(out), _stream(x))
     _lib.check(rc, "smoe_layernorm_rows")
     return out
@@ -1327,4 +1346,56 @@ def soft_ce_bwd(logits: torch.Tensor, rows: torch.Tensor, g: torch.Tensor, targe
                                       rows.data_ptr() + 4 * B, rows.data_ptr() + 8 * B, rows.data_ptr() + 12 * B, _ptr(g), _ptr(out),
                                       _stream(logits))
     _lib.check(rc, "smoe_soft_ce_bwd")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ knowledge distillation
+DISTILL_SOFT, DISTILL_HARD = 0, 1
+_DISTILL_MODES = {"soft": DISTILL_SOFT, "hard": DISTILL_HARD}
+
+
+def _distill_args(student, teacher, mode):
+    _chk(student, "student", ndim=2, align=2)
+    _chk(teacher, "teacher", ndim=2, align=2)
+    if mode not in _DISTILL_MODES:
+        raise RuntimeError(f"distill: mode must be 'soft' or 'hard', not {mode!r}")
+    if teacher.shape != student.shape or teacher.device != student.device:
+        raise RuntimeError("distill: student and teacher logits must be [B, C] on one device")
+    dtype_code(student.dtype), dtype_code(teacher.dtype)
+    return student.shape[0], student.shape[1], _DISTILL_MODES[mode]
+
+
+def distill_fwd(student: torch.Tensor, teacher: torch.Tensor, base_loss: torch.Tensor, mode: str, tau: float, alpha: float):
+    """losses.py:53-72 on the device (smoe_distill_fwd): ``student`` (the distillation head's logits) and ``teacher`` [B, C], each f32 /
+    f16 / bf16; ``base_loss`` a device f32 scalar.  -> (loss f32 [] = base (1 - alpha) + distill alpha, distill f32 [], row values
+    f64 [B], stats f64 [4, B], labels i32 [B]); the last two are what distill_bwd needs."""
+    B, C, m = _distill_args(student, teacher, mode)
+    _chk(base_loss, "base_loss", torch.float32, align=4)
+    if base_loss.numel() != 1 or base_loss.device != student.device:
+        raise RuntimeError("distill_fwd: base_loss must be a device f32 scalar")
+    dev = student.device
+    rows = torch.empty(B, dtype=torch.float64, device=dev)
+    stats = torch.empty((4, B), dtype=torch.float64, device=dev)
+    labels = torch.empty(B, dtype=torch.int32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)            # (distill, loss)
+    rc = _lib.load().smoe_distill_fwd(_ptr(student), dtype_code(student.dtype), _ptr(teacher), dtype_code(teacher.dtype), m, float(tau),
+                                      float(alpha), _ptr(base_loss), B, C, _ptr(rows), _ptr(stats), _ptr(labels), _ptr(out),
+                                      out.data_ptr() + 4, _stream(student))
+    _lib.check(rc, "smoe_distill_fwd")
+    return out[1], out[0], rows, stats, labels
+
+
+def distill_bwd(student: torch.Tensor, teacher: torch.Tensor, stats: torch.Tensor, labels: torch.Tensor, g: torch.Tensor, mode: str,
+                tau: float, alpha: float) -> torch.Tensor:
+    """d loss / d student in the student's dtype (smoe_distill_bwd); ``g``: device f32 scalar; ``stats`` / ``labels``: distill_fwd's."""
+    B, C, m = _distill_args(student, teacher, mode)
+    _chk(stats, "stats", torch.float64, 2, align=8)
+    _chk(labels, "labels", torch.int32, 1, align=4)
+    _chk(g, "g", torch.float32, align=4)
+    if tuple(stats.shape) != (4, B) or labels.numel() != B or g.numel() != 1 or g.device != student.device:
+        raise RuntimeError("distill_bwd: stats f64 [4, B], labels i32 [B] and a device f32 scalar g expected")
+    out = torch.empty_like(student)
+    rc = _lib.load().smoe_distill_bwd(_ptr(student), dtype_code(student.dtype), _ptr(teacher), dtype_code(teacher.dtype), m, float(tau),
+                                      float(alpha), B, C, _ptr(stats), _ptr(labels), _ptr(g), _ptr(out), _stream(student))
+    _lib.check(rc, "smoe_distill_bwd")
     return out

@@ -193,7 +193,7 @@ class SlimMoEFallbackWarning(UserWarning):
 _fallbacks_seen = set()
 
 
-def _warn_fallback(what: str, reason: str, shape) -> None:
+def _warn_fallback(what: str, reason: str, shape, stacklevel: int = 3) -> None:
     """One warning per (piece, reason, shape): the BASELINE shapes raise none (tests/test_gpu_model.py checks that)."""
     key = (what, reason, tuple(shape))
     if key in _fallbacks_seen:
@@ -201,7 +201,7 @@ def _warn_fallback(what: str, reason: str, shape) -> None:
     _fallbacks_seen.add(key)
     import warnings
     warnings.warn(f"{what}: shape {tuple(shape)} runs on a torch / vendor kernel, not on libslimmoe_hip ({reason})",
-                  SlimMoEFallbackWarning, stacklevel=3)
+                  SlimMoEFallbackWarning, stacklevel=stacklevel)
 
 
 def _linear16_reason(x16: torch.Tensor, weight: torch.Tensor):
@@ -542,6 +542,12 @@ class VisionTransformer(nn.Module):
               and n.weight.dtype == torch.float32)
         return n if ok else None
 
+    def _prefix_rows(self, B: int) -> tuple:
+        """The rows in front of the patch tokens: the class token and, in a distilled model, the distillation token."""
+        if self.dist_token is None:
+            return (self.cls_token.expand(B, -1, -1),)
+        return (self.cls_token.expand(B, -1, -1), self.dist_token.expand(B, -1, -1))
+
     def _embed(self, x, want_xn1: bool = False):
         """``pos_drop(cat(cls_token, patch_embed(x)) + pos_embed)`` (models/vision_transformer.py:818-824).  Under
         fp16-autocast inference the same arithmetic in three launches fewer: patch gather and the fp16 cast autocast
@@ -571,12 +577,15 @@ class VisionTransformer(nn.Module):
                 # class-token row, position embedding and -- when the first block takes it -- that block's norm1, in one pass
                 n1 = self._first_norm1()
                 ln = (n1.weight.detach(), n1.bias.detach() if n1.bias is not None else None, n1.eps) if (want_xn1 and n1 is not None) else None
-                out, xn1 = ops.embed_ln(tok, self.cls_token, self.pos_embed, B, gh * gw, ln=ln)
+                out, xn1 = ops.embed_ln(tok, self.cls_token, self.pos_embed, B, gh * gw, ln=ln, dist_token=self.dist_token)
                 return (out, xn1) if want_xn1 else out
             tok = tok.reshape(B, gh * gw, -1)
-            out = torch.empty((B, gh * gw + 1, tok.shape[-1]), dtype=torch.float32, device=x.device)
-            torch.add(tok, self.pos_embed[:, 1:], out=out[:, 1:])
+            nt = self.num_tokens
+            out = torch.empty((B, gh * gw + nt, tok.shape[-1]), dtype=torch.float32, device=x.device)
+            torch.add(tok, self.pos_embed[:, nt:], out=out[:, nt:])
             out[:, 0] = self.cls_token[0, 0] + self.pos_embed[0, 0]
+            if self.dist_token is not None:
+                out[:, 1] = self.dist_token[0, 0] + self.pos_embed[0, 1]
             return (out, None) if want_xn1 else out
         from . import dense
         if (type(pe) is PatchEmbed and dense.autocast_half_training(x) and x.dtype == torch.float32
@@ -590,11 +599,11 @@ class VisionTransformer(nn.Module):
             if dense.linear_supported(p2, pe.proj.weight):
                 tok = dense.LinearFn.apply(p2, pe.proj.weight, pe.proj.bias, None, _half_cache(self), torch.float16,
                                            "patch_embed_gemm").reshape(B, gh * gw, -1)
-                x = torch.cat((self.cls_token.expand(B, -1, -1), tok.float()), dim=1)
+                x = torch.cat(self._prefix_rows(B) + (tok.float(),), dim=1)
                 x = self.pos_drop(x + self.pos_embed)
                 return (x, None) if want_xn1 else x
         x = pe(x)
-        x = torch.cat((self.cls_token.expand(x.shape[0], -1, -1), x), dim=1)
+        x = torch.cat(self._prefix_rows(x.shape[0]) + (x,), dim=1)
         x = self.pos_drop(x + self.pos_embed)
         return (x, None) if want_xn1 else x
 
@@ -742,37 +751,94 @@ class VisionTransformer(nn.Module):
         return torch.cat(outs, dim=0)
 
     def forward(self, x):
-        f = self.forward_features(x)
-        if isinstance(self.head, nn.Linear) and _autocast_half_inference(f):
+        return self._head(self.head, self.forward_features(x), "head_gemm")
+
+    def _head(self, head, f, name: str):
+        """``head(f)`` for the feature rows ``f [B, d]``: under fp16 autocast on the own GEMM (inference: cached fp16 weights; training:
+        dense.LinearFn), else the module itself."""
+        if isinstance(head, nn.Linear) and _autocast_half_inference(f):
             hc = _half_cache(self)  # what autocast computes, minus the per-call weight casts
             if f.dtype == torch.float32 and f.is_contiguous():
                 from . import ops
                 f16 = ops.cast(f, torch.float16)
             else:
                 f16 = f.to(torch.float16)
-            out = _linear16(hc, f16.reshape(-1, f16.shape[-1]), self.head.weight, self.head.bias, name="head_gemm") if f16.dim() == 2 else None
+            out = _linear16(hc, f16.reshape(-1, f16.shape[-1]), head.weight, head.bias, name=name) if f16.dim() == 2 else None
             if out is not None:
                 return out
-            return F.linear(f16, hc.get(self.head.weight),
-                            hc.get(self.head.bias) if self.head.bias is not None else None)
+            return F.linear(f16, hc.get(head.weight),
+                            hc.get(head.bias) if head.bias is not None else None)
         from . import dense
-        if isinstance(self.head, nn.Linear) and f.dim() == 2 and dense.autocast_half_training(f) and DENSE_GEMM == "own":
+        if isinstance(head, nn.Linear) and f.dim() == 2 and dense.autocast_half_training(f) and DENSE_GEMM == "own":
             f16 = dense.cast16(f) if f.dtype == torch.float32 else f.contiguous()
-            if dense.linear_supported(f16, self.head.weight):
-                return dense.LinearFn.apply(f16, self.head.weight, self.head.bias, None, _half_cache(self), torch.float16,
-                                            "head_gemm")
-            _warn_fallback("head_gemm (training)", "K % 64 != 0", (f.shape[0], f.shape[1], self.head.weight.shape[0]))
-        elif isinstance(self.head, nn.Linear) and f.is_cuda and torch.is_autocast_enabled():
-            _warn_fallback("head_gemm", "config: needs fp16 autocast and a [B, d] feature matrix", tuple(f.shape))
-        return self.head(f)
+            if dense.linear_supported(f16, head.weight):
+                return dense.LinearFn.apply(f16, head.weight, head.bias, None, _half_cache(self), torch.float16,
+                                            name)
+            _warn_fallback(name + " (training)", "K % 64 != 0", (f.shape[0], f.shape[1], head.weight.shape[0]), stacklevel=4)
+        elif isinstance(head, nn.Linear) and f.is_cuda and torch.is_autocast_enabled():
+            _warn_fallback(name, "config: needs fp16 autocast and a [B, d] feature matrix", tuple(f.shape), stacklevel=4)   # (forward's caller)
+        return head(f)
 
 
-def _deit(embed_dim, default_depth, num_heads, pretrained=False, **kwargs):
+class DistilledVisionTransformer(VisionTransformer):
+    """DeiT's distilled ViT (models/model.py:32-77): a distillation token beside the class token, a position embedding for both, and a
+    second classifier ``head_dist`` on the distillation token.  Training: ``(head(x_cls), head_dist(x_dist))`` -- what
+    ``DistillationLoss`` takes; eval: the mean of the two.  State-dict keys and shapes are the reference's."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.num_tokens = 2
+        self.dist_token = nn.Parameter(torch.zeros(1, 1, self.embed_dim))
+        num_patches = self.patch_embed.num_patches
+        self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + 2, self.embed_dim))
+        self.head_dist = nn.Linear(self.embed_dim, self.num_classes) if self.num_classes > 0 else nn.Identity()
+        trunc_normal_(self.dist_token, std=0.02)
+        trunc_normal_(self.pos_embed, std=0.02)
+        self.head_dist.apply(_init_vit_weights)
+
+    def _final_norm_cls(self, x):
+        """``self.norm(x)[:, :2]``: the class-token and distillation-token rows [B, 2, d], normalised alone (LayerNorm is per token).
+        The own paths keep them as [2, B, d] underneath, so that each head reads contiguous rows."""
+        if isinstance(self.norm, nn.LayerNorm):
+            from . import dense
+            n = self.norm
+            if dense.autocast_half_training(x):
+                pre = x[:, :2].transpose(0, 1).contiguous()
+                if dense.layer_norm_supported(pre, n):
+                    return dense.layer_norm(pre, n, torch.float32).transpose(0, 1)
+            if (_autocast_half_inference(x) and x.dtype == torch.float32 and n.elementwise_affine and x.shape[-1] in _LN_DIMS
+                    and x.is_contiguous() and n.weight.dtype == torch.float32):
+                from . import ops
+                B, N, d = x.shape
+                out = torch.empty((2, B, d), dtype=torch.float32, device=x.device)
+                flat = x.reshape(-1)
+                bias = n.bias.detach() if n.bias is not None else None
+                for r in range(2):      # row r of every image, read in place, (P + 2) * d apart
+                    ops.layernorm_rows(flat[r * d:], N * d, B, d, n.weight.detach(), bias, n.eps, out=out[r])
+                return out.transpose(0, 1)
+            return n(x[:, :2])
+        return self.norm(x)[:, :2]
+
+    def forward_features(self, x):
+        f = super().forward_features(x)
+        return f[:, 0], f[:, 1]
+
+    def forward(self, x):
+        x, x_dist = self.forward_features(x)
+        x = self._head(self.head, x, "head_gemm")
+        x_dist = self._head(self.head_dist, x_dist, "head_dist_gemm")
+        if self.training:
+            return x, x_dist
+        return (x + x_dist) / 2          # inference: the average of both classifiers' predictions
+
+
+def _deit(embed_dim, default_depth, num_heads, pretrained=False, cls=None, **kwargs):
     if pretrained:
         raise RuntimeError("pretrained weights need network access (torch.hub); not available offline")
     depth = kwargs.pop("depth", default_depth)  # tests build shallow copies of the big configurations
-    return VisionTransformer(patch_size=16, embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=4,
-                             qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
+    model_cls = cls or VisionTransformer
+    return model_cls(patch_size=16, embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=4,
+                     qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), **kwargs)
 
 
 @register_model
@@ -785,3 +851,28 @@ def deit_tiny_patch16_224(pretrained=False, **kwargs):
 def deit_base_patch16_224(pretrained=False, **kwargs):
     """models/model.py:163-183."""
     return _deit(768, 12, 12, pretrained, **kwargs)
+
+
+@register_model
+def deit_tiny_distilled_patch16_224(pretrained=False, **kwargs):
+    """models/model.py:186-206."""
+    return _deit(192, 12, 3, pretrained, cls=DistilledVisionTransformer, **kwargs)
+
+
+@register_model
+def deit_small_distilled_patch16_224(pretrained=False, **kwargs):
+    """models/model.py:209-229."""
+    return _deit(384, 12, 6, pretrained, cls=DistilledVisionTransformer, **kwargs)
+
+
+@register_model
+def deit_base_distilled_patch16_224(pretrained=False, **kwargs):
+    """models/model.py:232-252."""
+    return _deit(768, 12, 12, pretrained, cls=DistilledVisionTransformer, **kwargs)
+
+
+@register_model
+def deit_base_distilled_patch16_384(pretrained=False, **kwargs):
+    """models/model.py:279-300 (N = 24 * 24 + 2 = 578 tokens: inside the attention kernels' reach)."""
+    kwargs.setdefault("img_size", 384)
+    return _deit(768, 12, 12, pretrained, cls=DistilledVisionTransformer, **kwargs)
