@@ -564,6 +564,33 @@ int smoe_soft_ce_fwd(const void* logits, int dtype, const float* target, const i
 int smoe_soft_ce_bwd(const void* logits, int dtype, const float* target, const int64_t* labels, float smoothing, int64_t B, int C,
                      const float* row_max, const float* row_logsum, const float* row_tsum, const float* g, void* dlogits, void* stream);
 
+/* ---- evaluation metrics (engine.py:99-113: `loss = criterion(output, target)`, `acc1, acc5 = accuracy(output, target, topk=(1, 5))`
+ * and three `.item()` reads per batch; timm.utils.accuracy) ------------------------------------------------------------------------------
+ * smoe_eval_metrics : logits [B, C] (f32 / f16 / bf16, computed in f32), labels i64 [B]; ks = a HOST array of nk values (1 <= nk <= 4,
+ *                     every k >= 1; read before the call returns).  Two launches, each logit read once.
+ *   row_loss f32 [B]  : the row's cross-entropy -- smoe_soft_ce_fwd's label form at smoothing 0, the same arithmetic in the same order:
+ *                       bit-equal to its row_loss for a label inside [0, C).
+ *   row_rank i32 [B]  : the number of classes that come before the label's class in a stable descending order of the row,
+ *                       #{c : x_c > x_t} + #{c < label : x_c == x_t} with x_t = logits[b, label], where a NaN is the largest value and
+ *                       two NaNs are equal (torch.topk's order); ties go to the LOWER index.  The label is in the top k iff row_rank < k.
+ *                       On a row without a logit equal to x_t this is what `output.topk(k, 1, True, True)` + `eq` decide; on a tie
+ *                       torch.topk's pick is unspecified and this rule is the contract.
+ *   batch f32 [1+nk]  : batch[0] = mean of row_loss, summed in smoe_soft_ce_fwd's fixed order (bit-equal to its *loss);
+ *                       batch[1 + i] = (count_i * 100) * f32(1 / B) in f32 with count_i = #{rows : row_rank < ks[i]} -- the bits of timm's
+ *                       `correct[:k].reshape(-1).float().sum(0) * 100.0 / B` as torch computes it on the device (a division by a host
+ *                       scalar is a multiplication by its f32 reciprocal there; up to one ulp from the true quotient).
+ *   acc f64 [2+nk]    : may be NULL.  acc[0] += sum of (double)row_loss[b] in a fixed order, acc[1] += B, acc[2 + i] += count_i: a
+ *                       plain read-add-write by one thread, ordered by the stream, NO atomics -- the epoch's meter without a host read
+ *                       per batch.  One accumulator used from two streams at once is the caller's error.
+ * Non-finite inputs and bad labels: a label outside [0, C) gives row_rank = INT32_MAX (never correct) and row_loss = NaN, and nothing
+ * is read out of bounds (where torch device-asserts).  A NaN or +inf logit, or a row of -inf, makes that row's loss NaN as in
+ * smoe_soft_ce_fwd; its rank still follows the rule above.  Other rows are untouched; batch[0] and acc[0] take the poison through the
+ * sum, the counts stay exact.
+ * 0 < C <= 2^30, B < 2^31.  16-byte accesses when C % 8 == 0 and logits is 16-byte aligned, element-wise otherwise.  B == 0 returns 0
+ * at once; arguments are checked before any launch; no allocation, no synchronisation: it can be captured.                            */
+int smoe_eval_metrics(const void* logits, int dtype, const int64_t* labels, int64_t B, int C, const int* ks, int nk,
+                      float* row_loss, int32_t* row_rank, float* batch, double* acc, void* stream);
+
 /* ---- knowledge distillation (main.py:688 `criterion = DistillationLoss(...)`; losses.py:53-72) -------------------------------------
  * The distillation term between the student's distillation logits and a teacher's logits, both [B, C], each f32 / f16 / bf16 with its
  * own dtype code, and its blend with the base loss.  mode 0 = soft, 1 = hard; tau > 0 (soft only); alpha.

@@ -111,6 +111,8 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "smoe_soft_ce_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "smoe_eval_metrics": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "smoe_distill_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_void_p, c_int64, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "smoe_distill_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int64, c_int, c_void_p,

@@ -11,6 +11,9 @@
 //   smoe_distill_fwd  : the distillation term between the student's distillation logits and a teacher's logits -- soft: KL(teacher ||
 //                       student) at temperature tau; hard: cross-entropy against the teacher's argmax -- and its blend with the base loss
 //   smoe_distill_bwd  : its gradient for the student's distillation logits (the teacher gets none)
+// and what the reference's evaluate() computes after every forward (engine.py:99-113):
+//   smoe_eval_metrics : per-row cross-entropy + the label's rank in one pass, then the batch's loss / top-k accuracies and an f64
+//                       accumulator for the epoch, all on the device (upstream: a dozen launches and three host reads)
 #include "smoe_common.h"
 #include <type_traits>
 
@@ -323,6 +326,136 @@ bool ce_vec_ok(const void* logits, const void* target, const void* dlogits, int 
 }
 
 constexpr int GRID_Y_MAX = 65535;
+
+// ---- evaluation metrics (engine.py:99-113: criterion, timm's accuracy() and three .item() reads per batch) -------------------------
+constexpr int EVAL_MAX_K = 4;
+struct TopK { int k[EVAL_MAX_K]; };
+
+// One workgroup per row: soft_ce_fwd_kernel's label form at smoothing 0 -- the same loads per thread, the same ce_step and the same
+// tree, so row_loss has its bits -- and, on the registers that pass holds anyway, the label's rank: the number of classes that come
+// before it in a stable descending order where a NaN is the largest value (torch.topk's order; ties go to the lower index).  The
+// label's logit x_t is one uniform load up front.  A label outside [0, C): nothing is loaded for it, rank INT32_MAX, loss NaN.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void eval_row_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels, int C,
+                                                                float* __restrict__ row_loss, int32_t* __restrict__ row_rank) {
+  __shared__ float red[2][LOSS_THREADS / 64];
+  __shared__ int redc[LOSS_THREADS / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const T* __restrict__ x = logits + (size_t)row * C;
+  const int64_t l = labels[row];
+  const bool valid = l >= 0 && l < C;
+  const int lab = valid ? (int)l : 0;
+  const float xt = valid ? to_f32<T>(x[lab]) : 0.f;
+  const bool tn = xt != xt;
+  MaxSum ms{-__builtin_inff(), 0.f};
+  int cnt = 0;
+  const int span = LOSS_THREADS * CE_K;
+  for (int c0 = 0; c0 < C; c0 += span) {
+    float v[CE_K];
+    bool ok[CE_K];
+    if constexpr (VEC) {     // C % 8 == 0 and an aligned base: 8 consecutive logits per lane
+      const int c = c0 + tid * CE_K;
+      const bool in = c < C;
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q) { ok[q] = in; v[q] = 0.f; }
+      if (in) load8(x + c, v);
+    } else {
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q) {
+        const int c = c0 + q * LOSS_THREADS + tid;
+        ok[q] = c < C;
+        v[q] = ok[q] ? to_f32<T>(x[c]) : 0.f;
+      }
+    }
+    ce_step(ms, v, ok);
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      const int c = VEC ? c0 + tid * CE_K + q : c0 + q * LOSS_THREADS + tid;
+      const bool vn = v[q] != v[q];
+      const bool before = !tn && (vn || v[q] > xt);          // x_c comes first whatever its index
+      const bool tie = tn ? vn : v[q] == xt;                 // ... or only from a lower index
+      cnt += (ok[q] && (before || (tie && c < lab))) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float m2 = __shfl_xor(ms.m, m, 64), s2 = __shfl_xor(ms.s, m, 64);
+    ms.merge(m2, s2);
+    cnt += __shfl_xor(cnt, m, 64);
+  }
+  if ((tid & 63) == 0) { red[0][tid >> 6] = ms.m; red[1][tid >> 6] = ms.s; redc[tid >> 6] = cnt; }
+  __syncthreads();
+  if (tid == 0) {
+    MaxSum a{red[0][0], red[1][0]}, b{red[0][2], red[1][2]};
+    a.merge(red[0][1], red[1][1]);
+    b.merge(red[0][3], red[1][3]);
+    a.merge(b.m, b.s);
+    float lse = a.m + logf(a.s);
+    if (!(fabsf(lse) <= 3.4028234664e38f)) lse = __builtin_nanf("");
+    row_loss[row] = valid ? lse - xt : __builtin_nanf("");
+    row_rank[row] = valid ? (redc[0] + redc[1]) + (redc[2] + redc[3]) : 0x7fffffff;
+  }
+}
+
+// One workgroup: batch[0] = the mean of row_loss on row_mean_kernel's tree (its bits); batch[1 + i] = (count_i * 100) * f32(1 / B) with
+// count_i = #{rows : rank < k_i} -- the f32 operations torch runs ON THE DEVICE for timm's `correct.float().sum() * 100.0 / B` (a
+// division by a host scalar is a multiplication by its reciprocal there; measured: a true division differs in 65 of 193 counts at
+// B = 192); acc (may be NULL) f64 [2 + nk] +=
+// (sum of the row losses in double, B, count_i): a plain read-add-write by one thread, ordered by the stream.  Every sum runs over
+// the same strided partial sums and the same tree whatever ran before: the same bits run to run.
+__global__ __launch_bounds__(LOSS_THREADS) void eval_batch_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_rank,
+                                                                  int B, TopK ks, int nk, float* __restrict__ batch,
+                                                                  double* __restrict__ acc) {
+  constexpr int NW = LOSS_THREADS / 64;
+  __shared__ float redf[NW];
+  __shared__ double redd[NW];
+  __shared__ int redc[EVAL_MAX_K][NW];
+  float sum = 0.f;
+  double dsum = 0.0;
+  int cnt[EVAL_MAX_K] = {0, 0, 0, 0};
+  for (unsigned r = threadIdx.x; r < (unsigned)B; r += LOSS_THREADS) {
+    const float v = row_loss[r];
+    const int rk = row_rank[r];
+    sum += v;
+    dsum += (double)v;
+#pragma unroll
+    for (int i = 0; i < EVAL_MAX_K; ++i) cnt[i] += (i < nk && rk < ks.k[i]) ? 1 : 0;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sum += __shfl_xor(sum, m, 64);
+    dsum += __shfl_xor(dsum, m, 64);
+#pragma unroll
+    for (int i = 0; i < EVAL_MAX_K; ++i) cnt[i] += __shfl_xor(cnt[i], m, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    redf[w] = sum;
+    redd[w] = dsum;
+#pragma unroll
+    for (int i = 0; i < EVAL_MAX_K; ++i) redc[i][w] = cnt[i];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    batch[0] = ((redf[0] + redf[1]) + (redf[2] + redf[3])) / (float)B;
+    const float inv_b = (float)(1.0 / (double)B);      // torch divides a device tensor by a host scalar as x * f32(1 / B)
+    if (acc) {
+      acc[0] += (redd[0] + redd[1]) + (redd[2] + redd[3]);
+      acc[1] += (double)B;
+    }
+    for (int i = 0; i < nk; ++i) {
+      const int n = (redc[i][0] + redc[i][1]) + (redc[i][2] + redc[i][3]);
+      batch[1 + i] = __fmul_rn(__fmul_rn((float)n, 100.f), inv_b);
+      if (acc) acc[2 + i] += (double)n;
+    }
+  }
+}
+
+template <typename T>
+void launch_eval_row(bool vec, int B, hipStream_t s, const void* logits, const int64_t* labels, int C, float* row_loss, int32_t* row_rank) {
+  if (vec) hipLaunchKernelGGL((eval_row_kernel<T, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, labels, C, row_loss, row_rank);
+  else hipLaunchKernelGGL((eval_row_kernel<T, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, labels, C, row_loss, row_rank);
+}
 
 // ---- distillation (losses.py:53-72) -----------------------------------------------------------------------------------------
 // The row kernels compute in DOUBLE (MaxSumD / distill_step are MaxSum / ce_step with a double sum): the soft term is a difference of
@@ -640,6 +773,32 @@ extern "C" int smoe_soft_ce_bwd(const void* logits, int dtype, const float* targ
     default: launch_ce_bwd<bf16_bits>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
   }
   SMOE_CHECK_LAUNCH("smoe_soft_ce_bwd");
+  return 0;
+}
+
+extern "C" int smoe_eval_metrics(const void* logits, int dtype, const int64_t* labels, int64_t B, int C, const int* ks, int nk,
+                                 float* row_loss, int32_t* row_rank, float* batch, double* acc, void* stream) {
+  SMOE_REQUIRE(B >= 0 && B < (1ll << 31) && C > 0 && C <= (1 << 30), "smoe_eval_metrics: bad sizes (0 <= B < 2^31, 0 < C <= 2^30)");
+  SMOE_REQUIRE(smoe_dtype_ok(dtype), "smoe_eval_metrics: bad dtype code %d", dtype);
+  SMOE_REQUIRE(nk >= 1 && nk <= EVAL_MAX_K, "smoe_eval_metrics: 1 <= nk <= 4 expected (got %d)", nk);
+  SMOE_REQUIRE(ks != nullptr, "smoe_eval_metrics: null pointer (ks, a host array)");
+  TopK tk{{0, 0, 0, 0}};
+  for (int i = 0; i < nk; ++i) {
+    SMOE_REQUIRE(ks[i] >= 1, "smoe_eval_metrics: every k must be >= 1 (ks[%d] = %d)", i, ks[i]);
+    tk.k[i] = ks[i];
+  }
+  if (B == 0) return 0;
+  SMOE_REQUIRE(logits && labels && row_loss && row_rank && batch, "smoe_eval_metrics: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(logits, nullptr, nullptr, C);
+  switch (dtype) {
+    case SMOE_F32: launch_eval_row<float>(vec, (int)B, s, logits, labels, C, row_loss, row_rank); break;
+    case SMOE_F16: launch_eval_row<f16>(vec, (int)B, s, logits, labels, C, row_loss, row_rank); break;
+    default: launch_eval_row<bf16_bits>(vec, (int)B, s, logits, labels, C, row_loss, row_rank); break;
+  }
+  SMOE_CHECK_LAUNCH("smoe_eval_metrics");
+  hipLaunchKernelGGL(eval_batch_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_loss, row_rank, (int)B, tk, nk, batch, acc);
+  SMOE_CHECK_LAUNCH("smoe_eval_metrics (batch)");
   return 0;
 }
 

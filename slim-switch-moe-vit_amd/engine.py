@@ -1,6 +1,7 @@
 """Eval harness mirroring the reference's engine.evaluate (engine.py:88-121): eval mode, no_grad,
 autocast on the GPU, cross-entropy + top-1/top-5, per-batch loop.  Returns the same dict keys plus
-images/sec.  MetricLogger / distributed meters are out of scope."""
+images/sec.  The loss / accuracy meters live on the device (EvalMeter: no host read per batch, one all_reduce
+under dist_eval); the rest of MetricLogger is out of scope."""
 from __future__ import annotations
 
 import time
@@ -162,25 +163,129 @@ class GraphedForward:
         return static_out.clone()        # (the graph's own output buffer is overwritten by the next replay)
 
 
+_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _kernel_takes(output, target, topk) -> bool:
+    """Whether smoe_eval_metrics takes this batch: 2-D contiguous f32 / f16 / bf16 logits on the GPU, 1-D integer labels beside them,
+    one to four k >= 1."""
+    return (isinstance(output, torch.Tensor) and isinstance(target, torch.Tensor) and output.is_cuda and output.dim() == 2
+            and output.dtype in (torch.float32, torch.float16, torch.bfloat16) and output.is_contiguous() and output.shape[1] >= 1
+            and output.data_ptr() % output.element_size() == 0
+            and target.dim() == 1 and target.dtype in _INT_DTYPES and target.device == output.device
+            and target.numel() == output.shape[0] and 1 <= len(topk) <= 4 and all(int(k) == k and k >= 1 for k in topk))
+
+
+def _labels_i64(target):
+    return target.contiguous() if target.dtype == torch.int64 else target.long()
+
+
 def accuracy(output: torch.Tensor, target: torch.Tensor, topk=(1,)):
-    """timm.utils.accuracy: top-k accuracy in percent."""
+    """timm.utils.accuracy: top-k accuracy in percent, a list of 0-d f32 tensors.  2-D contiguous f32 / f16 / bf16 logits on the GPU
+    with 1-D integer labels go through smoe_eval_metrics (two launches); anything else takes timm's lines.  The two agree wherever no
+    row has another logit equal to its label's logit; on such a tie torch.topk's pick is unspecified, and the kernel's rule is a stable
+    descending order (a NaN largest, ties to the lower index)."""
+    if _kernel_takes(output, target, topk) and output.shape[0] > 0:
+        from . import ops
+        batch = ops.eval_metrics(output, _labels_i64(target), None, tuple(int(k) for k in topk))[0]
+        return [batch[1 + i] for i in range(len(topk))]
+    return _accuracy_torch(output, target, topk)
+
+
+def _accuracy_torch(output: torch.Tensor, target: torch.Tensor, topk=(1,)):
+    """timm.utils.accuracy's own lines."""
     maxk = min(max(topk), output.shape[1])
     _, pred = output.topk(maxk, 1, True, True)
     correct = pred.t().eq(target.reshape(1, -1).expand_as(pred.t()))
     return [correct[: min(k, maxk)].reshape(-1).float().sum(0) * 100.0 / target.shape[0] for k in topk]
 
 
+def _metrics_mode(metrics) -> str:
+    """``metrics`` of evaluate() / EvalMeter: "device", "torch", or "auto" = SLIMMOE_EVAL_METRICS (default "device")."""
+    if metrics == "auto":
+        import os
+        metrics = os.environ.get("SLIMMOE_EVAL_METRICS", "device")
+    if metrics not in ("device", "torch"):
+        raise ValueError(f"metrics must be 'device', 'torch' or 'auto' (SLIMMOE_EVAL_METRICS), not {metrics!r}")
+    return metrics
+
+
+class EvalMeter:
+    """The evaluation loop's meters (the reference's MetricLogger around loss / acc1 / acc5, engine.py:99-118) as ONE f64 tensor on
+    ``device``: [sum of the row losses, rows, correct rows per k].  ``update(output, target)`` reads nothing back: on the GPU it is
+    smoe_eval_metrics' two launches (``metrics`` "device"; "auto" = SLIMMOE_EVAL_METRICS, default device), and inputs the kernel does
+    not take (CPU tensors, other dtypes or layouts; ``metrics="torch"``) are accumulated into the same tensor with torch operations.
+    ``synchronize_between_processes()`` is the reference's call of that name: one all_reduce of the tensor.  ``result()`` is the one
+    device read: {"loss", "acc<k>"..., "n"} with loss = sum of the row losses (f64) / n and acc<k> = 100 x correct / n.
+
+    Ties: a row counts as correct for k when fewer than k classes come before its label in a stable descending order -- a NaN is the
+    largest value, equal logits go by the lower index.  That is ``output.topk(k)`` + ``eq`` wherever no other logit equals the
+    label's; where one does, torch.topk's pick is unspecified and this rule decides (the torch path takes torch.topk's pick)."""
+
+    def __init__(self, device, topk=(1, 5), metrics="auto"):
+        self.topk = tuple(int(k) for k in topk)
+        if not self.topk or min(self.topk) < 1:
+            raise ValueError(f"topk must hold k >= 1, not {topk!r}")
+        self.mode = _metrics_mode(metrics)
+        self.acc = torch.zeros(2 + len(self.topk), dtype=torch.float64, device=device)
+
+    def reset(self):
+        self.acc.zero_()
+
+    @torch.no_grad()
+    def update(self, output: torch.Tensor, target: torch.Tensor):
+        if output.shape[0] == 0:
+            return
+        if self.mode == "device" and output.device == self.acc.device and _kernel_takes(output, target, self.topk):
+            from . import ops
+            ops.eval_metrics(output, _labels_i64(target), self.acc, self.topk)
+            return
+        rows = torch.nn.functional.cross_entropy(output.double(), target, reduction="none")
+        maxk = min(max(self.topk), output.shape[1])
+        _, pred = output.topk(maxk, 1, True, True)
+        correct = pred.t().eq(target.reshape(1, -1).expand_as(pred.t()))
+        counts = [correct[: min(k, maxk)].reshape(-1).sum(0, dtype=torch.float64) for k in self.topk]
+        n = torch.full((), float(output.shape[0]), dtype=torch.float64, device=rows.device)
+        self.acc += torch.stack([rows.sum(dtype=torch.float64), n] + counts).to(self.acc.device)
+
+    def synchronize_between_processes(self, group=None):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.acc, group=group)
+
+    def result(self) -> dict:
+        vals = self.acc.tolist()               # the one device read
+        n = max(vals[1], 1.0)
+        out = {"loss": vals[0] / n}
+        for i, k in enumerate(self.topk):
+            out[f"acc{k}"] = 100.0 * vals[2 + i] / n
+        out["n"] = int(vals[1])
+        return out
+
+
 @torch.no_grad()
 def evaluate(data_loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], model: torch.nn.Module, device,
-             autocast: bool = True, *, ep_speculative="auto", hip_graph="auto"):
+             autocast: bool = True, *, ep_speculative="auto", hip_graph="auto", metrics="auto", dist_eval: bool = False):
     """engine.py:88-121.  ``hip_graph`` (True / False / "auto" = on for single-rank GPU models unless SLIMMOE_EVAL_GRAPH=0): every
     batch shape's forward is captured once and replayed (GraphedForward: same bits, no launch gaps -- a third of the step of the
     reference's DeiT-Tiny models).  Under expert parallelism the harness owns the step, so it can run the exchange WITHOUT a host round trip
     per layer even for the reference's capacity-less NaiveGate: ``ep_speculative`` (alpha; "auto" = SLIMMOE_EP_ALPHA, default 1.5;
     None / 0 = off) sizes static slots of alpha x the balanced share (ep.set_speculative), and a batch whose routing does not fit
     -- reported by all ranks together -- is evaluated again on the counted exchange (ep.run_guarded): the metrics are those of the
-    counted exchange either way.  Returns the reference's dict keys plus images/sec and the number of repeated steps."""
+    counted exchange either way.  Returns the reference's dict keys plus images/sec and the number of repeated steps.
+
+    ``metrics`` ("device" / "torch" / "auto" = SLIMMOE_EVAL_METRICS, default device): "device" keeps the loss and the top-1 / top-5
+    counts in an ``EvalMeter`` -- two launches per batch, no host read until the end of the loop, so the host queues the next batch
+    while this one runs; "torch" is the reference's lines (CrossEntropyLoss, timm's accuracy, three ``.item()`` per batch).  Under
+    "device" ``loss`` is the sum of the row losses in f64 over n (not the mean of per-batch f32 means), and acc1 / acc5 are the same
+    numbers wherever no row has another logit equal to its label's; on such a tie torch.topk's pick is unspecified, the meter's rule is
+    a stable descending order (EvalMeter).  A step that expert parallelism drops and repeats is counted once: the meter is updated
+    after ep.run_guarded returns.  ``dist_eval``: sum the meter over the ranks (``synchronize_between_processes``) before it is read
+    ("device" only; default False = this rank's numbers, as before)."""
     from . import ep
+    mode = _metrics_mode(metrics)
+    if dist_eval and mode != "device":
+        raise ValueError("evaluate(dist_eval=True) sums the device meter over the ranks: it needs metrics='device'")
     criterion = torch.nn.CrossEntropyLoss()
     model.eval()
     dev = torch.device(device)
@@ -193,6 +298,7 @@ def evaluate(data_loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], model: to
         hip_graph = os.environ.get("SLIMMOE_EVAL_GRAPH", "1") != "0"
     graphed = GraphedForward(model, autocast) if (hip_graph and GraphedForward.supported(model, dev, ep_graph)) else None
     n, loss_sum, a1, a5, repeats = 0, 0.0, 0.0, 0.0, 0
+    meter = EvalMeter(dev, (1, 5), "device") if mode == "device" else None
     t0 = time.perf_counter()
     for images, target in data_loader:
         images = images.to(dev, non_blocking=True)
@@ -201,21 +307,32 @@ def evaluate(data_loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], model: to
         def step():
             with torch.autocast(device_type=dev.type, dtype=torch.float16, enabled=autocast and dev.type == "cuda"):
                 output = graphed(images) if graphed is not None else model(images)
-                return output, criterion(output, target)
-        # (flush: this step's overflow report is read before its numbers are -- the .item() below waits for the batch anyway)
+                return output, (criterion(output, target) if meter is None else None)
+        # (flush: this step's overflow report is read before its numbers are -- under expert parallelism that read stays)
         (output, loss), again = ep.run_guarded(step, flush=True)
         repeats += int(again)
-        acc1, acc5 = accuracy(output, target, topk=(1, 5))
+        if meter is not None:        # after run_guarded: a step that was dropped and repeated is counted once
+            meter.update(output, target)
+            continue
+        acc1, acc5 = _accuracy_torch(output, target, topk=(1, 5))      # ("torch" = the reference's lines throughout, for A/B runs)
         bs = images.shape[0]
         n += bs
         loss_sum += loss.item() * bs
         a1 += acc1.item() * bs
         a5 += acc5.item() * bs
+    if meter is not None:
+        if dist_eval:
+            meter.synchronize_between_processes()
+        res = meter.result()         # the loop's one read of the metrics
+        n = max(res["n"], 1)
+        mean = (res["loss"], res["acc1"], res["acc5"])
+    else:
+        n = max(n, 1)
+        mean = (loss_sum / n, a1 / n, a5 / n)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    n = max(n, 1)
-    return {"loss": loss_sum / n, "acc1": a1 / n, "acc5": a5 / n, "images_per_sec": n / dt, "ep_repeated_steps": repeats,
+    return {"loss": mean[0], "acc1": mean[1], "acc5": mean[2], "images_per_sec": n / dt, "ep_repeated_steps": repeats,
             "hip_graph": graphed is not None}
 
 

@@ -6,6 +6,7 @@ Shapes / dtypes / contiguity are validated here, before the C call (SURVEY.md 8b
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -1347,6 +1348,47 @@ def soft_ce_bwd(logits: torch.Tensor, rows: torch.Tensor, g: torch.Tensor, targe
                                       _stream(logits))
     _lib.check(rc, "smoe_soft_ce_bwd")
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------- evaluation metrics
+_topk_arrays = {}     # topk tuple -> the host int array smoe_eval_metrics reads (built once per tuple)
+
+
+def eval_metrics(logits: torch.Tensor, labels: torch.Tensor, acc: Optional[torch.Tensor] = None, topk=(1, 5)):
+    """Cross-entropy and top-k accuracy of a batch in two launches (smoe_eval_metrics): ``logits`` f32 / f16 / bf16 [B, C], ``labels``
+    i64 [B], ``topk`` one to four k >= 1.  -> (batch f32 [1 + nk] = mean loss and the accuracies in percent, row_loss f32 [B], row_rank
+    i32 [B] = the classes that come before the label's in a stable descending order, NaN largest, ties to the lower index).  ``acc``
+    (optional): an f64 [2 + nk] accumulator on the logits' device, += (sum of the row losses, B, correct counts) -- no host read; use
+    one accumulator from one stream at a time."""
+    _chk(logits, "logits", ndim=2, align=2)
+    B, C = logits.shape
+    _chk(labels, "labels", torch.int64, 1, align=8)
+    if labels.numel() != B or labels.device != logits.device:
+        raise RuntimeError("eval_metrics: labels must be i64 [B] on the logits' device")
+    ks = tuple(int(k) for k in topk)
+    if not 1 <= len(ks) <= 4 or min(ks) < 1:
+        raise RuntimeError(f"eval_metrics: topk must hold one to four k >= 1, not {topk!r}")
+    if C < 1:
+        raise RuntimeError("eval_metrics: logits [B, C] with C >= 1 expected")
+    nk = len(ks)
+    if acc is not None:
+        _chk(acc, "acc", torch.float64, 1, align=8)
+        if acc.numel() != 2 + nk or acc.device != logits.device:
+            raise RuntimeError(f"eval_metrics: acc must be f64 [{2 + nk}] on the logits' device")
+    dev = logits.device
+    code = dtype_code(logits.dtype)
+    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+    row_rank = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:       # (the library returns at once: the mean of no rows is NaN, as torch's is)
+        return torch.full((1 + nk,), float("nan"), dtype=torch.float32, device=dev), row_loss, row_rank
+    batch = torch.empty(1 + nk, dtype=torch.float32, device=dev)
+    karr = _topk_arrays.get(ks)
+    if karr is None:
+        karr = _topk_arrays[ks] = (ctypes.c_int * nk)(*ks)
+    rc = _lib.load().smoe_eval_metrics(_ptr(logits), code, _ptr(labels), B, C, karr, nk, _ptr(row_loss), _ptr(row_rank), _ptr(batch),
+                                       _ptr(acc), _stream(logits))
+    _lib.check(rc, "smoe_eval_metrics")
+    return batch, row_loss, row_rank
 
 
 # ------------------------------------------------------------------------------------------------------------ knowledge distillation
