@@ -210,6 +210,17 @@ size_t smoe_dispatch_plan_workspace_bytes(int64_t n, int E);
 int smoe_dispatch_plan(const int64_t* idx, int64_t n, int E, int64_t capacity,
                        int32_t* counts, int32_t* offsets, int64_t* pos, int64_t* inv_pos,
                        int64_t* idx_pruned, void* workspace, size_t workspace_bytes, void* stream);
+/* smoe_dispatch_plan_subset: the plan over a PERIODIC SUBSET of the flat entries -- entry i is dispatched iff i % period < prefix
+ * (0 <= prefix <= period < 2^31; for "the first p of every P tokens" of a top-k pass: period = P * k, prefix = p * k).  Every other
+ * entry is read as -1: counts / offsets / pos are the full plan restricted to the dispatched entries, in the same stable order
+ * (expert, then flat index); pos[s] and inv_pos[i] keep numbering the entries of the FULL idx (what smoe_grouped_gemm's a_gather /
+ * row_map take: no compacted copy of tokens, idx or scores exists), pos[s] = -1 for s >= offsets[E], inv_pos[i] = -1 for an entry
+ * that is not dispatched.  idx = -1 keeps its meaning, empty groups are ordinary.  No capacity (a capacity rank is defined over all
+ * entries).  period == 0: every entry -- bit for bit smoe_dispatch_plan(capacity = -1).  Same workspace.  What it is for: the last
+ * block of an eval forward, whose classifier reads the class-token rows only (vit.VisionTransformer.tail_rows_only). */
+int smoe_dispatch_plan_subset(const int64_t* idx, int64_t n, int E, int64_t period, int64_t prefix, int32_t* counts,
+                              int32_t* offsets, int64_t* pos, int64_t* inv_pos, void* workspace, size_t workspace_bytes,
+                              void* stream);
 /* smoe_dispatch_plan_hist: the same plan from a chunk histogram the fused router wrote (smoe_ln_router_topk / smoe_gate_ln_router
  * `chunk_hist`; hist_chunk = tokens per row x k flat entries): one launch, no counting pass over idx.  Falls back to
  * smoe_dispatch_plan when the table does not fit the fused kernel.  idx here is what the plan is built over (for the gated MoE

@@ -13,6 +13,9 @@
 // the offsets from the whole table in LDS (a few KB) -- so the plan is two launches instead of four.
 // Upstream orders slots by atomicSub race; here slot order is ascending flat index (deterministic),
 // and with a capacity an entry is kept iff its raw rank in its expert is < capacity.
+// SUBSET (period > 0; smoe_dispatch_plan_subset): only the flat entries i with i % period < prefix are dispatched -- the counting
+// and the assign kernel read every other entry as -1, so counts / offsets / pos are the full plan restricted to those entries, in
+// the same stable order, and pos / inv_pos keep numbering the rows of the full tensors.  period == 0: every entry, as ever.
 #include "smoe_common.h"
 #include <type_traits>
 
@@ -25,8 +28,13 @@ constexpr int PLAN_CH = PLAN_THREADS * PLAN_ITERS;              // entries per w
 constexpr int PLAN_FUSED_MAX = 8192;                            // table entries the fused assign re-reads per workgroup
 constexpr int PLAN_FUSED_E = 64;
 
+// (n < 2^31, 0 <= prefix <= period < 2^31: the launcher checks)
+__device__ __forceinline__ bool plan_in_subset(int64_t i, int period, int prefix) {
+  return period == 0 || (uint32_t)i % (uint32_t)period < (uint32_t)prefix;
+}
+
 __global__ __launch_bounds__(PLAN_THREADS) void plan_count_kernel(const int64_t* __restrict__ idx, int64_t n, int E,
-                                                                  int32_t* __restrict__ blockcnt) {
+                                                                  int32_t* __restrict__ blockcnt, int period, int prefix) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t* hist = reinterpret_cast<int32_t*>(smem);
   for (int e = threadIdx.x; e < E; e += PLAN_THREADS) hist[e] = 0;
@@ -35,7 +43,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void plan_count_kernel(const int64_t*
 #pragma unroll
   for (int it = 0; it < PLAN_ITERS; ++it) {
     const int64_t i = base + it * PLAN_THREADS + threadIdx.x;
-    if (i < n) {
+    if (i < n && plan_in_subset(i, period, prefix)) {
       const int64_t e = idx[i];
       if (e >= 0 && e < E) atomicAdd(&hist[(int)e], 1);  // ids outside [0, E) count as dropped (-1)
     }
@@ -83,7 +91,8 @@ __global__ __launch_bounds__(PLAN_THREADS) void plan_assign_kernel(
     const int32_t* __restrict__ offsets_in, int64_t* __restrict__ pos, int64_t* __restrict__ inv_pos,
     int64_t* __restrict__ idx_pruned, int nblk, int32_t* __restrict__ counts_out, int32_t* __restrict__ offsets_out,
     int64_t slot_stride, int32_t* __restrict__ group_end_out, int tab_rows, int tab_ratio,
-    int32_t* __restrict__ raw_out = nullptr, const int32_t* __restrict__ slot_base = nullptr, int hdr_rows = 0) {
+    int32_t* __restrict__ raw_out = nullptr, const int32_t* __restrict__ slot_base = nullptr, int hdr_rows = 0, int period = 0,
+    int prefix = 0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // run[w][e]: raw rank of the next entry of expert e seen by wave w (wave w owns a contiguous quarter of the chunk)
   int32_t* run = reinterpret_cast<int32_t*>(smem);  // [PLAN_WAVES][E]
@@ -190,7 +199,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void plan_assign_kernel(
   for (int it = 0; it < PLAN_ITERS; ++it) {
     const int64_t i = wave_base + it * 64 + lane;
     int64_t e = -1;
-    if (i < n) e = idx[i];
+    if (i < n && plan_in_subset(i, period, prefix)) e = idx[i];    // (an entry outside the subset: not dispatched, as idx = -1)
     if (e >= E || e < 0) e = -1;                  // (before pass 2 narrows it to int: the low word of a 64-bit id outside [0, E) may lie inside)
     myidx[it] = e;
     if (e >= 0) atomicAdd(&run[wave * E + (int)e], 1);
@@ -502,7 +511,7 @@ extern "C" size_t smoe_dispatch_plan_workspace_bytes(int64_t n, int E) {
 static int plan_impl(const int64_t* idx, int64_t n, int E, int64_t capacity, int32_t* counts, int32_t* offsets, int64_t* pos,
                      int64_t* inv_pos, int64_t* idx_pruned, void* workspace, size_t workspace_bytes, void* stream,
                      int64_t slot_stride, int32_t* group_end, int32_t* raw_counts = nullptr, const int32_t* slot_base = nullptr,
-                     int hdr_rows = 0) {
+                     int hdr_rows = 0, int period = 0, int prefix = 0) {
   SMOE_REQUIRE(counts && offsets && workspace, "smoe_dispatch_plan: null pointer");
   SMOE_REQUIRE(n >= 0 && n < (1ll << 31), "smoe_dispatch_plan: n=%lld out of range", (long long)n);
   SMOE_REQUIRE(E >= 1 && E <= 8192, "smoe_dispatch_plan: E=%d out of range [1, 8192]", E);
@@ -519,12 +528,12 @@ static int plan_impl(const int64_t* idx, int64_t n, int E, int64_t capacity, int
   const bool fused = n > 0 && E <= PLAN_FUSED_E && nblk * E <= PLAN_FUSED_MAX;
   SMOE_REQUIRE(fused || (slot_stride == 0 && !slot_base), "smoe_dispatch_plan_padded / _slots: the padded layouts need E <= %d and ceil(n / %d) * E <= %d",
                PLAN_FUSED_E, PLAN_CH, PLAN_FUSED_MAX);
-  hipLaunchKernelGGL(plan_count_kernel, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)E * 4, s, idx, n, E, blockcnt);
+  hipLaunchKernelGGL(plan_count_kernel, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)E * 4, s, idx, n, E, blockcnt, period, prefix);
   SMOE_CHECK_LAUNCH("smoe_dispatch_plan/count");
   if (fused) {
     hipLaunchKernelGGL(plan_assign_kernel<true>, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)(PLAN_WAVES * E + 5 * E + 2) * 4, s,
                        idx, n, E, capacity, blockcnt, nullptr, pos, inv_pos, idx_pruned, (int)nblk, counts, offsets, slot_stride,
-                       group_end, (int)nblk, 1, raw_counts, slot_base, hdr_rows);
+                       group_end, (int)nblk, 1, raw_counts, slot_base, hdr_rows, period, prefix);
     SMOE_CHECK_LAUNCH("smoe_dispatch_plan/assign_fused");
     return 0;
   }
@@ -532,7 +541,7 @@ static int plan_impl(const int64_t* idx, int64_t n, int E, int64_t capacity, int
   hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(scan_threads), (size_t)E * 4, s, blockcnt, (int)nblk, E, capacity, rawbase, counts, offsets);
   SMOE_CHECK_LAUNCH("smoe_dispatch_plan/scan");
   if (n > 0) {
-    hipLaunchKernelGGL(plan_assign_kernel<false>, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)PLAN_WAVES * E * 4, s, idx, n, E, capacity, rawbase, offsets, pos, inv_pos, idx_pruned, (int)nblk, nullptr, nullptr, (int64_t)0, nullptr, 0, 1);
+    hipLaunchKernelGGL(plan_assign_kernel<false>, dim3((int)nblk), dim3(PLAN_THREADS), (size_t)PLAN_WAVES * E * 4, s, idx, n, E, capacity, rawbase, offsets, pos, inv_pos, idx_pruned, (int)nblk, nullptr, nullptr, (int64_t)0, nullptr, 0, 1, nullptr, nullptr, 0, period, prefix);
     SMOE_CHECK_LAUNCH("smoe_dispatch_plan/assign");
     int tb = (int)((n + 255) / 256);
     if (tb > 1024) tb = 1024;
@@ -546,6 +555,19 @@ extern "C" int smoe_dispatch_plan(const int64_t* idx, int64_t n, int E, int64_t 
                                   int32_t* offsets, int64_t* pos, int64_t* inv_pos, int64_t* idx_pruned,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   return plan_impl(idx, n, E, capacity, counts, offsets, pos, inv_pos, idx_pruned, workspace, workspace_bytes, stream, 0, nullptr);
+}
+
+// The plan over a periodic subset of the flat entries: entry i is dispatched iff i % period < prefix (period == 0: every entry,
+// bit for bit smoe_dispatch_plan without a capacity).  For "the first p of every P tokens" of a top-k routing pass period = P * k,
+// prefix = p * k.  No capacity: a capacity rank is defined over all entries.  Empty groups are ordinary (counts[e] = 0).
+extern "C" int smoe_dispatch_plan_subset(const int64_t* idx, int64_t n, int E, int64_t period, int64_t prefix, int32_t* counts,
+                                         int32_t* offsets, int64_t* pos, int64_t* inv_pos, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  SMOE_REQUIRE(period >= 0 && period < (1ll << 31) && prefix >= 0 && prefix <= period,
+               "smoe_dispatch_plan_subset: need 0 <= prefix <= period < 2^31 (period=%lld prefix=%lld)", (long long)period,
+               (long long)prefix);
+  return plan_impl(idx, n, E, -1, counts, offsets, pos, inv_pos, nullptr, workspace, workspace_bytes, stream, 0, nullptr, nullptr,
+                   nullptr, 0, (int)period, (int)prefix);
 }
 
 // The plan from a chunk histogram the router already made (smoe_ln_router_topk / smoe_gate_ln_router `chunk_hist`): hist[c][e] =

@@ -303,12 +303,20 @@ class FMoETransformerMLP(nn.Module):
     def ep_active(self) -> bool:
         return self.world_size > 1 or bool(getattr(self, "force_ep", False))
 
-    def forward_norm_add_steps(self, x: torch.Tensor, norm: nn.Module, next_norm: Optional[nn.Module] = None):
+    def forward_norm_add_steps(self, x: torch.Tensor, norm: nn.Module, next_norm: Optional[nn.Module] = None,
+                               tail: Optional[tuple] = None):
         """Generator form of ``forward_norm_add``: under expert parallelism it yields at the points where this
         micro-batch waits for the host or for an all-to-all (ep.ep_forward_steps) so that the caller can interleave
         another micro-batch; otherwise it never yields.  The result is the generator's return value.  With ``next_norm``
         (the LayerNorm that reads the result next) the expert-parallel combine also produces ``next_norm(result)`` in
-        16 bit and the return value is the pair."""
+        16 bit and the return value is the pair.
+
+        ``tail`` = (period, prefix) in rows: the caller reads only the rows r with r % period < prefix of the result (the
+        class-token rows, after the last block).  LayerNorm + router still run over all rows -- ``last_plan[0]`` / ``[1]`` are
+        complete -- but the plan, GEMM-1 and GEMM-2 cover those rows alone (same kernels, and a row of these GEMMs depends on
+        its own operand row only: the same bits); every other row of the result holds the residual ``x``.  A hint: ignored
+        under expert parallelism, with a capacity gate (a capacity rank is defined over the whole batch) and wherever this
+        falls back to the unfused composition.  With it the result may be ``x``'s own memory, written in place."""
         cd = self.compute_dtype or default_compute_dtype()
         g = self.gate
         ok = (x.is_cuda and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine
@@ -339,12 +347,16 @@ class FMoETransformerMLP(nn.Module):
         noise = g.make_noise(T, x2.device) if is_switch else None
         gw = g.gate.weight.detach().float().contiguous()
         gb = g.gate.bias.detach().float() if g.gate.bias is not None else None
-        hist = ops.chunk_hist(T, d, g.tot_expert, k, x2.device)   # the router pass also counts for the plan (count_by_gate folded in)
+        cap = g.capacity(T)
+        sub = None                # (period, prefix): the rows the experts run for, when the caller reads no others
+        if tail is not None and cap < 0 and tail[0] > 0 and T % tail[0] == 0 and 0 < tail[1] < tail[0]:
+            sub = (int(tail[0]), int(tail[1]))
+        # the router pass also counts for the plan (count_by_gate folded in) -- over all rows: of no use to a plan over some
+        hist = ops.chunk_hist(T, d, g.tot_expert, k, x2.device) if sub is None else None
         xn16, _, idx, score, _, probs = ops.ln_router_topk(
             x2, norm.weight.detach().float(), norm.bias.detach().float() if norm.bias is not None else None, norm.eps,
             gw, gb, k, g.kind, noise, xn16_dtype=cd, want_probs=is_switch, hist=hist)
-        cap = g.capacity(T)
-        counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap, hist=hist)
+        counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap, hist=hist, subset=sub)
         self.last_plan = (idx, score, counts, offsets, pos, inv_pos)
         if is_switch:
             from .autograd import switch_aux_loss
@@ -360,6 +372,22 @@ class FMoETransformerMLP(nn.Module):
             out, xn_next = ops.gather_combine_ln(y, inv_pos, score, T, k, x2, next_norm.weight.detach().float(),
                                                  next_norm.bias.detach().float(), next_norm.eps, torch.float16)
             return out.reshape(shape), xn_next.reshape(shape)
+        if sub is not None:
+            # the slots that can exist, known without asking the device: the GEMMs' row bound (tile plan, grid) and the length of
+            # their row lists.  pos numbers rows of the full tensors, so GEMM-1 gathers from the whole xn16 and GEMM-2 writes rows
+            # of the whole result.  k = 1: in place over the residual image (GEMM-2's epilogue loads an output element's residual
+            # and stores the element from the same thread, and `residual` / `out` are not __restrict__: the residual-MoE half has
+            # always aliased them) -- the rows no expert ran for ARE the residual, without a copy.  k > 1: the combine walks all
+            # rows and finds no slot (inv_pos = -1) for the others: 0 + residual.
+            # The k = 1 GEMM-2 of a few dozen rows per group runs on the 128 x 128 one-workgroup-per-tile kernel (variant 1: twice
+            # the workgroups, half the tile height; 69 -> 55 us at ViT-B / 256 images, profiles/r13_tail_rows.md): the same MFMA instruction over K in the
+            # same order and the same epilogue arithmetic as the persistent kernel, one thread per output element from residual
+            # load to store -- bit-equal to it on these shapes (tests/test_gpu_tail_rows.py).
+            pos_sub = pos[:(T // sub[0]) * sub[1] * k]
+            out = self._gathered_tail(xn16, operands, cd, offsets, pos_sub, inv_pos, score, residual=x2,
+                                      out=x2 if k == 1 else None, allow_fused=False,
+                                      gemm2_variant=1 if self.gemm_variant == 9 else None)
+            return out.reshape(shape)
         out = (x2.clone() if cap >= 0 else torch.empty_like(x2)) if k == 1 else None   # (k > 1: the combine allocates it)
         out = self._gathered_tail(xn16, operands, cd, offsets, pos, inv_pos, score, residual=x2, out=out,
                                   allow_fused=x2.dtype == torch.float32)
@@ -373,10 +401,11 @@ class FMoETransformerMLP(nn.Module):
         b2 = ex.h4toh.bias.detach().float() if ex.h4toh.bias is not None else None
         return w1, b1, w2, b2
 
-    def _gathered_tail(self, xn16, operands, cd, offsets, pos, inv_pos, score, residual, out, allow_fused=True):
+    def _gathered_tail(self, xn16, operands, cd, offsets, pos, inv_pos, score, residual, out, allow_fused=True, gemm2_variant=None):
         """The single-rank expert FFN behind a fused norm + router pass: GEMM-1 gathers its rows from the un-permuted 16-bit image
         ``xn16`` (the scatter folded into its operand fetch); for k = 1 GEMM-2's store does the combine and the residual add into
-        ``out``, else GEMM-2 is followed by the combine (into ``out``, or into a new tensor when it is None).  Returns the result."""
+        ``out``, else GEMM-2 is followed by the combine (into ``out``, or into a new tensor when it is None).  Returns the result.
+        ``gemm2_variant``: another kernel for the k = 1 GEMM-2 (default: this module's ``gemm_variant``)."""
         w1, b1, w2, b2 = operands
         k = self.top_k
         # k = 1: both expert GEMMs as ONE persistent launch (optional build, ops.FFN_FUSED); same arithmetic tile for tile as the
@@ -388,7 +417,7 @@ class FMoETransformerMLP(nn.Module):
         h = ops.grouped_gemm(xn16, w1, b1, offsets, ops.EPI_GELU, cd, variant=self.gemm_variant, a_gather=pos, a_div=k)
         if k == 1:
             return ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, residual.dtype, row_map=pos, row_scale=score.reshape(-1),
-                                    out=out, variant=self.gemm_variant, residual=residual)
+                                    out=out, variant=self.gemm_variant if gemm2_variant is None else gemm2_variant, residual=residual)
         y = ops.grouped_gemm(h, w2, b2, offsets, ops.EPI_NONE, cd, variant=self.gemm_variant)
         return ops.gather_combine(y, inv_pos, score, residual.shape[0], k, residual.dtype, residual=residual, out=out)
 

@@ -515,10 +515,12 @@ def zero_row_output(bg: Optional[torch.Tensor], k: int, w2: torch.Tensor, b1: Op
 
 
 def dispatch_plan(idx: torch.Tensor, E: int, capacity: int = -1, want_pruned: Optional[bool] = None,
-                  hist: Optional[torch.Tensor] = None):
+                  hist: Optional[torch.Tensor] = None, subset: Optional[tuple] = None):
     """(counts i32 [E], offsets i32 [E+1], pos i64 [n], inv_pos i64 [n], idx_pruned i64 [n] | None).  ``hist``: the chunk histogram the
     fused router filled for exactly this ``idx`` (chunk_hist / ln_router_topk / gate_ln_router): the plan then skips its counting
-    launch (smoe_dispatch_plan_hist)."""
+    launch (smoe_dispatch_plan_hist).  ``subset`` = (period, prefix) in tokens: only the tokens t with t % period < prefix are
+    dispatched (smoe_dispatch_plan_subset; no capacity, and a router histogram -- it counted every token -- is not used): the
+    first ``offsets[E]`` entries of ``pos`` hold their flat entries, expert by expert, and ``inv_pos`` is -1 everywhere else."""
     _chk(idx, "idx", torch.int64, align=8)  # read element-wise: slices of a [T,k] tensor are fine
     flat = idx.reshape(-1)
     n = flat.numel()
@@ -533,8 +535,16 @@ def dispatch_plan(idx: torch.Tensor, E: int, capacity: int = -1, want_pruned: Op
     pos = torch.empty(n, dtype=torch.int64, device=dev)
     inv_pos = torch.empty(n, dtype=torch.int64, device=dev)
     pruned = torch.empty(n, dtype=torch.int64, device=dev) if want_pruned else None
+    if subset is not None:
+        period, prefix = int(subset[0]), int(subset[1])
+        if capacity >= 0 or want_pruned or not 0 <= prefix <= period:
+            raise RuntimeError(f"dispatch_plan: subset=({period}, {prefix}) needs capacity < 0 (no idx_pruned) and 0 <= prefix <= period")
+        kk = idx.shape[1] if idx.dim() == 2 else 1          # flat entries per token
     with _timed("plan", {"bytes": n * 24}, idx):
-        if hist is not None:
+        if subset is not None:
+            rc = lib.smoe_dispatch_plan_subset(_ptr(flat), n, E, period * kk, prefix * kk, _ptr(counts), _ptr(offsets), _ptr(pos),
+                                               _ptr(inv_pos), _ptr(ws), ws_bytes, _stream(idx))
+        elif hist is not None:
             _chk(hist, "hist", torch.int32, 2)
             k = idx.shape[1] if idx.dim() == 2 else 1      # flat entries per token
             rc = lib.smoe_dispatch_plan_hist(_ptr(flat), n, E, int(capacity), _ptr(hist), int(hist.tok) * k, _ptr(counts), _ptr(offsets),

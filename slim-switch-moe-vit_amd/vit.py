@@ -425,13 +425,15 @@ class Block(nn.Module):
         f = mask.div_(keep)
         return f, f.repeat_interleave(x.shape[1])
 
-    def forward_steps(self, x, xn1=None, next_norm=None):
+    def forward_steps(self, x, xn1=None, next_norm=None, tail=None):
         """The block as a generator (result = return value): it yields only inside an expert-parallel MoE ``mlp``, at
         the points where this micro-batch waits for the host or an all-to-all (ep.ep_forward_steps).
 
         ``xn1``: ``norm1(x)`` already computed by the previous block's combine (see ``next_norm``).  ``next_norm``: the NEXT
         block's ``norm1``; when this block's expert-parallel combine can produce that LayerNorm in the same pass
-        (smoe_gather_combine_ln) the result is ``(x, norm1_next(x))`` instead of ``x``.
+        (smoe_gather_combine_ln) the result is ``(x, norm1_next(x))`` instead of ``x``.  ``tail`` = (period, prefix): the caller
+        reads only the rows t with t % period < prefix of every image's result; handed to the fused MoE half as a hint
+        (FMoETransformerMLP.forward_norm_add_steps), which then runs its experts for those rows alone.
 
         Stochastic depth (``x + drop_path(f(norm(x)))``, models/vision_transformer.py:319-322): inactive = the plain fused paths;
         active (training) = the per-sample ``mask / keep`` factor travels as a per-row scale into the stores that add the
@@ -475,6 +477,8 @@ class Block(nn.Module):
                 # x + mlp(norm2(x)): LN + router, scatter, combine + add all fused
                 fuse_next = (next_norm is not None and _autocast_half_inference(x) and isinstance(next_norm, nn.LayerNorm)
                              and next_norm.elementwise_affine and x.dtype == torch.float32 and x.shape[-1] in _LN_DIMS)
+                if tail is not None:
+                    return (yield from steps(x, self.norm2, next_norm=next_norm if fuse_next else None, tail=tail))
                 return (yield from steps(x, self.norm2, next_norm=next_norm if fuse_next else None))
             fused = getattr(self.mlp, "forward_add", None)
             if fused is not None:
@@ -625,7 +629,7 @@ class VisionTransformer(nn.Module):
         x, xn1 = self._embed(x, want_xn1=True)
         if x.is_cuda and not torch.is_grad_enabled():   # (generator form: every block is handed the next block's norm1)
             from .ep import drain
-            x = drain(self._blocks_steps(x, xn1))
+            x = drain(self._blocks_steps(x, xn1, head_rows_only=True))
         else:
             x = self.blocks(x)
         return self.pre_logits(self._final_norm_cls(x))
@@ -709,9 +713,28 @@ class VisionTransformer(nn.Module):
                 ep = True
         return n if ep else 1
 
-    def _blocks_steps(self, x, xn0=None):
+    tail_rows_only = True    # eval: the last block's experts run for the rows the classifier reads only (False: for every row)
+
+    def _tail_rows(self, x, blk):
+        """``(tokens per image, rows the head reads)`` when the LAST block's expert FFN may leave out every other row, else None.
+        ``_final_norm_cls`` normalises rows [0, num_tokens) of every image and nothing else reads the last block's output; the
+        block's attention half, LayerNorm + router and ``last_plan`` stay whole.  Only where nothing else is in play: eval without
+        grad on the GPU, a LayerNorm as final norm (per row), a fused single-rank MoE half behind a gate that never drops (a
+        capacity rank is defined over the whole batch)."""
+        m = getattr(blk, "mlp", None)
+        if (not self.tail_rows_only or not x.is_cuda or x.dim() != 3 or torch.is_grad_enabled() or self.training
+                or not isinstance(self.norm, nn.LayerNorm) or not 0 < self.num_tokens < x.shape[1]
+                or type(self)._final_norm_cls not in (VisionTransformer._final_norm_cls, DistilledVisionTransformer._final_norm_cls)
+                or type(blk).forward_steps is not Block.forward_steps
+                or not hasattr(m, "forward_norm_add_steps") or not hasattr(m, "ep_active") or m.ep_active()
+                or m.gate.capacity(1 << 20) >= 0):
+            return None
+        return (int(x.shape[1]), int(self.num_tokens))
+
+    def _blocks_steps(self, x, xn0=None, head_rows_only=False):
         """``self.blocks(x)`` as a generator, handing every block the next block's ``norm1`` so that an expert-parallel
-        combine can produce it on the way out (one pass over the residual stream less per layer)."""
+        combine can produce it on the way out (one pass over the residual stream less per layer).  ``head_rows_only``: the
+        caller hands the result to ``_final_norm_cls`` and to nothing else (see ``_tail_rows``)."""
         blocks = list(self.blocks)
         xn = xn0                 # norm1(x) of block 0 when the embedding pass produced it (_embed)
         for i, blk in enumerate(blocks):
@@ -720,7 +743,11 @@ class VisionTransformer(nn.Module):
                 continue
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
             nn1 = nxt.norm1 if (nxt is not None and hasattr(nxt, "forward_steps") and "forward" not in nxt.__dict__) else None
-            r = yield from blk.forward_steps(x, xn1=xn, next_norm=nn1)
+            tail = self._tail_rows(x, blk) if (head_rows_only and nxt is None) else None
+            if tail is not None:
+                r = yield from blk.forward_steps(x, xn1=xn, next_norm=nn1, tail=tail)
+            else:
+                r = yield from blk.forward_steps(x, xn1=xn, next_norm=nn1)
             x, xn = r if isinstance(r, tuple) else (r, None)
         return x
 
@@ -729,7 +756,7 @@ class VisionTransformer(nn.Module):
 
     def _features_steps(self, x):
         x, xn1 = self._embed(x, want_xn1=True)
-        x = yield from self._blocks_steps(x, xn1)
+        x = yield from self._blocks_steps(x, xn1, head_rows_only=True)
         return self.pre_logits(self._final_norm_cls(x))
 
     def _forward_features_pipelined(self, x, n: int):
