@@ -57,7 +57,7 @@ const char* smoe_last_error(void);
  * models/resmoe_flop_hook.py:7-8; selected at models/resMoE.py:26-29).
  *   logits = x @ wg^T + bg           routing decided as if accumulated in f64 and rounded once to f32:
  *                                    f32 fast path with a rigorous error bound, f64 re-do of a token when a
- *                                    deciding gap is inside the bound (gate_kind | 0x100 forces f64 for all)
+ *                                    deciding gap is inside the bound (gate_kind | SMOE_ROUTER_ALL_F64 forces f64 for all)
  *   NAIVE : (val, idx) = top-k(logits) [ties: lowest expert id; descending logit]; score = softmax(val)
  *   SWITCH: k == 1; p = softmax(logits + noise) over all E; idx = argmax; score = p[idx];
  *           probs (may be NULL) receives p [T,E] for the aux loss.
@@ -65,9 +65,12 @@ const char* smoe_last_error(void);
  * idx [T,k] i64, score [T,k] f32, logits_out [T,E] f32 or NULL.
  * Requires d % 8 == 0, d <= 2048, 1 <= k <= E, k <= 4.  workspace: smoe_router_workspace_bytes(T) bytes
  * (redo counter + list of tokens handed to the f64 pass).  The calls clear the counter words with a small launch of
- * their own -- unless the caller keeps ONE workspace per stream and says so (gate_kind | 0x200; smoe_gate_ln_router:
- * with_ln | 2): every redo pass leaves the counter words zero on its way out, so a workspace that was zero before its
- * first use stays ready, and the clearing launch in front of every router call disappears.                          */
+ * their own -- unless the caller keeps ONE workspace per stream and says so (gate_kind | SMOE_ROUTER_WS_KEPT_ZERO;
+ * smoe_gate_ln_router: with_ln | 2): every redo pass leaves the counter words zero on its way out, so a workspace that was
+ * zero before its first use stays ready, and the clearing launch in front of every router call disappears.  (An all-f64 call
+ * with LayerNorm runs its f32 pass without a redo pass behind it: it is not to be combined with a kept workspace.)      */
+#define SMOE_ROUTER_ALL_F64 0x100      /* gate_kind flag of smoe_router_topk / smoe_ln_router_topk: every token through the f64 pass */
+#define SMOE_ROUTER_WS_KEPT_ZERO 0x200 /* gate_kind flag of the same two: the workspace's counter words are zero on entry */
 size_t smoe_router_workspace_bytes(int64_t T);
 int smoe_router_topk(const void* x, int x_dtype, const float* wg, const float* bg, const float* noise,
                      int64_t T, int d, int E, int k, int gate_kind,

@@ -4,75 +4,57 @@
 //                          MoE router in front of the experts
 //   smoe_zero_row_output : what every skipped (all-zero) token receives from the MoE, computed once per layer
 // The kernel is router16_kernel (router16_kernel.h) with GATE = 1 (gate + router) or 2 (gate only).
-#include "router16_kernel.h"
+#include "router_launch.h"
 
 namespace {
 using namespace r16;
 
-struct GLnArgs {
-  const float* g; const float* b; float eps; void* xn16; int xn16_dtype; float* xn32;
-  int32_t* hist = nullptr;   // chunk histogram for the dispatch plan (gate + router only), or NULL
-};
-
-template <int NJ, bool LN, typename NT, int GATE>
-int launch_gate(const float* x, const GLnArgs& ln, const SkipGateArgs& ga, const float* wg, const float* bg, int64_t T, int d,
-                int E, int k, int32_t* rc, int32_t* rl, int64_t* idx, float* score, hipStream_t s, bool ws_zero) {
+template <int NJ, bool LN, typename NT, int GATE> int launch_gate(const RouterArgs& a) {
   constexpr int EB = 8;
   constexpr size_t smem = router16_smem<NJ, LN, EB, GATE>();
   const int64_t tok_per_block = (R16_THREADS / 64) * 4;
-  int64_t need = (T + tok_per_block - 1) / tok_per_block;
+  int64_t need = (a.T + tok_per_block - 1) / tok_per_block;
   constexpr int64_t max_wg = 768;
   const int64_t iters = (need + max_wg - 1) / max_wg;
   const int grid = (int)(need < 1 ? 1 : (need + iters - 1) / (iters < 1 ? 1 : iters));
-  HistArgs ha{GATE == 1 ? ln.hist : nullptr, R16_HIST_TOK};
-  const int grid0 = ha.hist ? (int)((T + R16_HIST_TOK - 1) / R16_HIST_TOK) : grid;
-  if (!ws_zero) {   // (a kept workspace is zero already: the redo pass clears its counter words on the way out)
-    hipError_t me = smoe_zero_words(rc, 4, s);
-    if (me != hipSuccess) {
-      smoe_set_error("smoe_gate_ln_router: counter clear failed: %s", hipGetErrorString(me));
-      return (int)me;
-    }
-  }
+  // with a chunk histogram (gate + router only) every workgroup of the f32 pass walks ONE contiguous chunk of R16_HIST_TOK tokens
+  const HistArgs ha{GATE == 1 ? a.hist : nullptr, R16_HIST_TOK};
+  const int grid0 = ha.hist ? (int)((a.T + R16_HIST_TOK - 1) / R16_HIST_TOK) : grid;
+  // (there is no all-f64 mode here: grid_f64 only bounds the redo pass)
+  const RouterPlan plan{grid0, grid, 16, LN, "smoe_gate_ln_router/f32", "smoe_gate_ln_router/f64", "smoe_gate_ln_router/redo"};
   if (smem > 64 * 1024) {
     SMOE_ENSURE_SMEM(router16_kernel<float, NJ, 0, LN, NT, EB, GATE>);
     SMOE_ENSURE_SMEM(router16_kernel<float, NJ, 1, LN, NT, EB, GATE>);
   }
-#define G_LAUNCH(MODE, GRID)                                                                                          \
-  hipLaunchKernelGGL((router16_kernel<float, NJ, MODE, LN, NT, EB, GATE>), dim3(GRID), dim3(R16_THREADS), smem, s, x,   \
-                     ln.g, ln.b, ln.eps, (NT*)ln.xn16, ln.xn32, wg, bg, (const float*)nullptr, T, d, E, k,            \
-                     (int)SMOE_GATE_NAIVE, rc, rl, idx, score, (float*)nullptr, (float*)nullptr, ga, ha)
-  G_LAUNCH(0, grid0);
-  SMOE_CHECK_LAUNCH("smoe_gate_ln_router/f32");
-  G_LAUNCH(1, (grid < 16 ? grid : 16));
-  SMOE_CHECK_LAUNCH("smoe_gate_ln_router/redo");
+#define G_LAUNCH(MODE, g, rc, rl)                                                                                             \
+  hipLaunchKernelGGL((router16_kernel<float, NJ, MODE, LN, NT, EB, GATE>), dim3(g), dim3(R16_THREADS), smem, a.stream,        \
+                     (const float*)a.x, a.ln_g, a.ln_b, a.ln_eps, (NT*)a.xn16, a.xn32, a.wg, a.bg, a.noise, a.T, a.d, a.E,    \
+                     a.k, a.gate_kind, rc, rl, a.idx, a.score, a.logits, a.probs, a.gate, ha)
+  return run_router_passes(
+      a, plan, [&](int g, int32_t* rc, int32_t* rl) { G_LAUNCH(0, g, rc, rl); },
+      [&](int g, int32_t* rc, int32_t* rl) { G_LAUNCH(1, g, rc, rl); });
 #undef G_LAUNCH
-  return 0;
 }
 
-template <bool LN, typename NT, int GATE>
-int gate_by_d(const float* x, const GLnArgs& ln, const SkipGateArgs& ga, const float* wg, const float* bg, int64_t T, int d,
-              int E, int k, int32_t* rc, int32_t* rl, int64_t* idx, float* score, hipStream_t s, bool ws_zero) {
-  switch (d) {
-    case 192: return launch_gate<3, LN, NT, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
-    case 384: return launch_gate<6, LN, NT, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
-    case 768: return launch_gate<12, LN, NT, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
-    case 1024: return launch_gate<16, LN, NT, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
+// LayerNorm on / off x the 16-bit image's type (instantiated for both types without LayerNorm as well) x d
+template <int GATE> int dispatch_gate(const RouterArgs& a) {
+#define GATE_BY_D(LN, NT)                                    \
+  switch (a.d) {                                             \
+    case 192: return launch_gate<3, LN, NT, GATE>(a);        \
+    case 384: return launch_gate<6, LN, NT, GATE>(a);        \
+    case 768: return launch_gate<12, LN, NT, GATE>(a);       \
+    case 1024: return launch_gate<16, LN, NT, GATE>(a);      \
+  }                                                          \
+  break
+  switch ((a.ln_on ? 2 : 0) | (a.xn16_dtype == SMOE_BF16 ? 1 : 0)) {
+    case 0: GATE_BY_D(false, f16);
+    case 1: GATE_BY_D(false, bf16_bits);
+    case 2: GATE_BY_D(true, f16);
+    case 3: GATE_BY_D(true, bf16_bits);
   }
-  smoe_set_error("smoe_gate_ln_router: unsupported d=%d", d);
+#undef GATE_BY_D
+  smoe_set_error("smoe_gate_ln_router: unsupported d=%d", a.d);
   return 1;
-}
-
-template <int GATE>
-int gate_by_ln(bool with_ln, const float* x, const GLnArgs& ln, const SkipGateArgs& ga, const float* wg, const float* bg,
-               int64_t T, int d, int E, int k, int32_t* rc, int32_t* rl, int64_t* idx, float* score, hipStream_t s,
-               bool ws_zero) {
-  const bool bf = ln.xn16_dtype == SMOE_BF16;
-  if (with_ln) {
-    if (bf) return gate_by_d<true, bf16_bits, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
-    return gate_by_d<true, f16, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
-  }
-  if (bf) return gate_by_d<false, bf16_bits, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
-  return gate_by_d<false, f16, GATE>(x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
 }
 
 // out[c] = sum_j score_j (sum_h W2[e_j][c,h] gelu(b1[e_j][h]) + b2[e_j][c]);  (e_j, score_j) = the NaiveGate routing of an
@@ -235,16 +217,23 @@ extern "C" int smoe_gate_ln_router(const void* x, int x_dtype, int with_ln, cons
   SMOE_REQUIRE(T > 0 && T < (1ll << 31), "smoe_gate_ln_router: bad T");
   SMOE_REQUIRE(E == 0 || (wg && idx && score), "smoe_gate_ln_router: router outputs missing");
   SMOE_REQUIRE(xn16_dtype == SMOE_F16 || xn16_dtype == SMOE_BF16, "smoe_gate_ln_router: xn16 must be f16 or bf16");
-  SMOE_REQUIRE(workspace && workspace_bytes >= 16 + (((size_t)T * 4 + 15) & ~(size_t)15), "smoe_gate_ln_router: workspace too small");
-  int32_t* rc = reinterpret_cast<int32_t*>(workspace);
-  int32_t* rl = reinterpret_cast<int32_t*>((char*)workspace + 16);
-  GLnArgs ln{ln_gamma, ln_beta, ln_eps, xn16, xn16_dtype, xn32};
-  ln.hist = (chunk_hist && E > 0 && 1024 % (R16_HIST_TOK * k) == 0) ? chunk_hist : nullptr;
-  SkipGateArgs ga{gate_w, gate_b, threshold, skip_count, mask, zero_out, E > 0 ? idx_plan : nullptr, tk32};
-  hipStream_t s = (hipStream_t)stream;
-  const bool ws_zero = (with_ln & 2) != 0;   // bit 1: the caller keeps the workspace's counter words zero between calls
-  if (E == 0) return gate_by_ln<2>((with_ln & 1) != 0, (const float*)x, ln, ga, nullptr, nullptr, T, d, 0, 1, rc, rl, nullptr, nullptr, s, ws_zero);
-  return gate_by_ln<1>((with_ln & 1) != 0, (const float*)x, ln, ga, wg, bg, T, d, E, k, rc, rl, idx, score, s, ws_zero);
+  RouterArgs a{};
+  a.entry = "smoe_gate_ln_router";
+  a.x = x, a.x_dtype = x_dtype;
+  a.ln_on = (with_ln & 1) != 0, a.ln_g = ln_gamma, a.ln_b = ln_beta, a.ln_eps = ln_eps;
+  a.xn16 = xn16, a.xn16_dtype = xn16_dtype, a.xn32 = xn32;
+  a.T = T, a.d = d, a.gate_kind = SMOE_GATE_NAIVE;
+  a.gate = SkipGateArgs{gate_w, gate_b, threshold, skip_count, mask, zero_out, E > 0 ? idx_plan : nullptr, tk32};
+  a.ws_kept_zero = (with_ln & 2) != 0;  // with_ln bit 1: what SMOE_ROUTER_WS_KEPT_ZERO is in the router entry points' gate_kind
+  a.stream = (hipStream_t)stream;
+  if (int rc = router_take_workspace(a, workspace, workspace_bytes)) return rc;
+  if (E == 0) {  // gate only: no router operands, no routing outputs
+    a.k = 1;
+    return dispatch_gate<2>(a);
+  }
+  a.wg = wg, a.bg = bg, a.E = E, a.k = k, a.idx = idx, a.score = score;
+  a.hist = (chunk_hist && 1024 % (R16_HIST_TOK * k) == 0) ? chunk_hist : nullptr;
+  return dispatch_gate<1>(a);
 }
 
 extern "C" int smoe_zero_row_output(const float* bg, int E, int k, const float* w2, const float* b1, const float* b2, int d,

@@ -13,7 +13,7 @@
 // eight experts at a time; router weights in LDS as f32.  The 8 per-lane partial sums of a group of 8
 // experts are reduced with a transposed butterfly (10 shuffles instead of 48): afterwards lanes with
 // equal (lane>>3) hold the full logit of expert 4*b5 + 2*b4 + b3 of the group.
-#include "smoe_common.h"
+#include "router_launch.h"
 
 namespace {
 
@@ -313,80 +313,60 @@ __global__ __launch_bounds__(ROUTER_THREADS, (MODE == 0 ? 4 : 2)) void router_ke
 }
 
 template <typename XT, int NCH>
-int launch_router(const void* x, const float* wg, const float* bg, const float* noise, int64_t T, int d, int E,
-                  int k, int gate_kind, int force_f64, int32_t* redo_count, int32_t* redo_list, int64_t* idx,
-                  float* score, float* logits_out, float* probs, hipStream_t stream) {
-  const int Epad = (E + 7) & ~7;
+int launch_router(const RouterArgs& a) {
+  const int Epad = (a.E + 7) & ~7;
   const size_t logit_bytes = ((size_t)(ROUTER_WAVES + 1) * Epad * 4 + 15) & ~(size_t)15;
-  const size_t w_bytes = (size_t)Epad * d * 4;
-  const bool w_lds = (logit_bytes + w_bytes) <= 64 * 1024;
+  const size_t w_bytes = (size_t)Epad * a.d * 4;
+  const bool w_lds = (logit_bytes + w_bytes) <= 64 * 1024;  // never above the default dynamic-LDS limit: no attribute to ensure
   const size_t smem = logit_bytes + (w_lds ? w_bytes : 0);
-  int64_t need = (T + ROUTER_WAVES - 1) / ROUTER_WAVES;
+  int64_t need = (a.T + ROUTER_WAVES - 1) / ROUTER_WAVES;
   const int grid = (int)(need < 2048 ? (need < 1 ? 1 : need) : 2048);
-#define ROUTER_LAUNCH(WL, MODE, GRID, RC, RL)                                                                      \
-  hipLaunchKernelGGL((router_kernel<XT, NCH, WL, MODE>), dim3(GRID), dim3(ROUTER_THREADS), smem, stream,          \
-                     (const XT*)x, wg, bg, noise, T, d, E, k, gate_kind, RC, RL, idx, score, logits_out, probs)
-  const bool ws_zero = (force_f64 & 2) != 0;
-  force_f64 &= 1;
-  if (force_f64) {
-    if (w_lds) ROUTER_LAUNCH(true, 1, grid, nullptr, nullptr);
-    else ROUTER_LAUNCH(false, 1, grid, nullptr, nullptr);
-    SMOE_CHECK_LAUNCH("smoe_router_topk/f64");
-    return 0;
-  }
-  if (!ws_zero) {
-    hipError_t me = smoe_zero_words(redo_count, 4, stream);
-    if (me != hipSuccess) {
-      smoe_set_error("smoe_router_topk: counter clear failed: %s", hipGetErrorString(me));
-      return (int)me;
-    }
-  }
-  if (w_lds) ROUTER_LAUNCH(true, 0, grid, redo_count, redo_list);
-  else ROUTER_LAUNCH(false, 0, grid, redo_count, redo_list);
-  SMOE_CHECK_LAUNCH("smoe_router_topk/f32");
-  const int redo_grid = grid < 32 ? grid : 32;  // the redo list is short (~1e-4 T); surplus waves exit at once
-  if (w_lds) ROUTER_LAUNCH(true, 1, redo_grid, redo_count, redo_list);
-  else ROUTER_LAUNCH(false, 1, redo_grid, redo_count, redo_list);
-  SMOE_CHECK_LAUNCH("smoe_router_topk/redo");
+  // one grid for every pass; the redo pass is capped at 32 workgroups where the other three launchers cap at 16 (historical)
+  const RouterPlan plan{grid, grid, 32, false, "smoe_router_topk/f32", "smoe_router_topk/f64", "smoe_router_topk/redo"};
+#define ROUTER_LAUNCH(WL, MODE, g, rc, rl)                                                                              \
+  hipLaunchKernelGGL((router_kernel<XT, NCH, WL, MODE>), dim3(g), dim3(ROUTER_THREADS), smem, a.stream, (const XT*)a.x, \
+                     a.wg, a.bg, a.noise, a.T, a.d, a.E, a.k, a.gate_kind, rc, rl, a.idx, a.score, a.logits, a.probs)
+  return run_router_passes(
+      a, plan,
+      [&](int g, int32_t* rc, int32_t* rl) {
+        if (w_lds) ROUTER_LAUNCH(true, 0, g, rc, rl);
+        else ROUTER_LAUNCH(false, 0, g, rc, rl);
+      },
+      [&](int g, int32_t* rc, int32_t* rl) {
+        if (w_lds) ROUTER_LAUNCH(true, 1, g, rc, rl);
+        else ROUTER_LAUNCH(false, 1, g, rc, rl);
+      });
 #undef ROUTER_LAUNCH
-  return 0;
 }
 
-template <typename XT>
-int dispatch_nch(const void* x, const float* wg, const float* bg, const float* noise, int64_t T, int d, int E,
-                 int k, int gate_kind, int f64, int32_t* rc, int32_t* rl, int64_t* idx, float* score,
-                 float* logits_out, float* probs, hipStream_t s) {
-  const int nch = (d + 255) / 256;
-  switch (nch) {
-    case 1: return launch_router<XT, 1>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 2: return launch_router<XT, 2>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 3: return launch_router<XT, 3>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 4: return launch_router<XT, 4>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 5: return launch_router<XT, 5>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 6: return launch_router<XT, 6>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 7: return launch_router<XT, 7>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
-    case 8: return launch_router<XT, 8>(x, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, logits_out, probs, s);
+template <typename XT> int dispatch_nch(const RouterArgs& a) {
+  switch ((a.d + 255) / 256) {
+#define NCH_CASE(N) case N: return launch_router<XT, N>(a)
+    NCH_CASE(1); NCH_CASE(2); NCH_CASE(3); NCH_CASE(4); NCH_CASE(5); NCH_CASE(6); NCH_CASE(7); NCH_CASE(8);
+#undef NCH_CASE
   }
-  smoe_set_error("smoe_router_topk: d=%d unsupported (d <= 2048)", d);
+  smoe_set_error("smoe_router_topk: d=%d unsupported (d <= 2048)", a.d);
   return 1;
 }
 
 }  // namespace
 
-int smoe_router16_try(const void* x, int x_dtype, const float* wg, const float* bg, const float* noise, int64_t T,
-                      int d, int E, int k, int gate_kind, int force_f64, int32_t* rc, int32_t* rl, int64_t* idx,
-                      float* score, float* logits_out, float* probs, hipStream_t s);  // router16.hip
-
 // workspace: [16 B: redo counter][T x i32 redo list]
 extern "C" size_t smoe_router_workspace_bytes(int64_t T) { return T < 0 ? 0 : 16 + (((size_t)T * 4 + 15) & ~(size_t)15); }
 
-// gate_kind bit 8 (0x100) forces the all-f64 path (test hook: every token through the f64 kernel)
+// gate_kind carries SMOE_ROUTER_ALL_F64 (test hook: every token through the f64 kernel) and SMOE_ROUTER_WS_KEPT_ZERO
 extern "C" int smoe_router_topk(const void* x, int x_dtype, const float* wg, const float* bg, const float* noise,
                                 int64_t T, int d, int E, int k, int gate_kind, int64_t* idx, float* score,
                                 float* logits_out, float* probs, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  const int force_f64 = ((gate_kind & 0x100) ? 1 : 0) | ((gate_kind & 0x200) ? 2 : 0);   // bit 1: counter words kept zero by the caller
-  gate_kind &= 0xff;
+  RouterArgs a{};
+  a.entry = "smoe_router_topk";
+  a.x = x, a.x_dtype = x_dtype;
+  a.wg = wg, a.bg = bg, a.noise = noise;
+  a.T = T, a.d = d, a.E = E, a.k = k;
+  a.idx = idx, a.score = score, a.logits = logits_out, a.probs = probs;
+  a.stream = (hipStream_t)stream;
+  router_decode_gate_kind(a, gate_kind);
   if (T == 0) return 0;  // empty batch: nothing to route (zero-sized tensors have null data pointers)
   SMOE_REQUIRE(x && wg && idx && score, "smoe_router_topk: null pointer");
   SMOE_REQUIRE(T >= 0 && T < (1ll << 31) && d > 0 && E > 0, "smoe_router_topk: bad sizes T=%lld d=%d E=%d", (long long)T, d, E);
@@ -394,24 +374,11 @@ extern "C" int smoe_router_topk(const void* x, int x_dtype, const float* wg, con
   SMOE_REQUIRE(k >= 1 && k <= E && k <= ROUTER_MAX_K, "smoe_router_topk: k=%d out of range (E=%d, max %d)", k, E,
                ROUTER_MAX_K);
   SMOE_REQUIRE(E <= 4096, "smoe_router_topk: E=%d too large", E);
-  SMOE_REQUIRE(gate_kind == SMOE_GATE_NAIVE || gate_kind == SMOE_GATE_SWITCH, "smoe_router_topk: bad gate_kind %d",
-               gate_kind);
-  SMOE_REQUIRE(gate_kind != SMOE_GATE_SWITCH || k == 1, "smoe_router_topk: switch gate needs k == 1");
-  SMOE_REQUIRE(workspace && workspace_bytes >= smoe_router_workspace_bytes(T), "smoe_router_topk: workspace too small");
-  if (T == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  int32_t* rc = reinterpret_cast<int32_t*>(workspace);
-  int32_t* rl = reinterpret_cast<int32_t*>((char*)workspace + 16);
-  {
-    const int r16 = smoe_router16_try(x, x_dtype, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score,
-                                      logits_out, probs, s);
-    if (r16 != -1) return r16;
-  }
-  switch (x_dtype) {
-    case SMOE_F32: return dispatch_nch<float>(x, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-    case SMOE_F16: return dispatch_nch<f16>(x, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-    case SMOE_BF16: return dispatch_nch<bf16_bits>(x, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-  }
-  smoe_set_error("smoe_router_topk: bad x_dtype %d", x_dtype);
-  return 1;
+  SMOE_REQUIRE(a.gate_kind == SMOE_GATE_NAIVE || a.gate_kind == SMOE_GATE_SWITCH, "smoe_router_topk: bad gate_kind %d",
+               a.gate_kind);
+  SMOE_REQUIRE(a.gate_kind != SMOE_GATE_SWITCH || k == 1, "smoe_router_topk: switch gate needs k == 1");
+  if (int rc = router_take_workspace(a, workspace, workspace_bytes)) return rc;
+  const int r16 = smoe_router16_try(a);
+  if (r16 != -1) return r16;
+  return router_by_x_dtype(a, [&](auto xt) { return dispatch_nch<decltype(xt)>(a); });
 }

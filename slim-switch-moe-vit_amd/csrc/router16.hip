@@ -1,7 +1,7 @@
 // Router, 16-lanes-per-token layout (E <= 8 at d in {192, 384, 768, 1024}; E <= 32 at d in {768, 1024}): the fast
 // path of smoe_router_topk, the fused LayerNorm + router, and the LayerNorm kernel.  The kernel template lives in
 // router16_kernel.h (shared with gate.hip, which instantiates the token-skip-gate variants).
-#include "router16_kernel.h"
+#include "router_launch.h"
 #include "router_mt_kernel.h"
 #include <cstdlib>
 
@@ -136,65 +136,35 @@ int ln_dispatch_nj(const void* x, const float* g, const float* b, float eps, int
   return 0;
 }
 
-struct LnArgs {
-  const float* g; const float* b; float eps; void* xn16; int xn16_dtype; float* xn32; bool on;
-  int32_t* hist = nullptr;   // chunk histogram for the dispatch plan (E <= 8 images only), or NULL
-};
-
-template <typename XT, int NJ, bool LN, typename NT, int EB>
-int launch16(const void* x, const LnArgs& ln, const float* wg, const float* bg, const float* noise, int64_t T, int d,
-             int E, int k, int gate_kind, int force_f64, int32_t* rc, int32_t* rl, int64_t* idx, float* score,
-             float* logits_out, float* probs, hipStream_t s) {
+template <typename XT, int NJ, bool LN, typename NT, int EB> int launch16(const RouterArgs& a) {
   // 32 experts: the f32 weight image (96-128 KB) leaves room for ONE workgroup per CU; 512 threads put 8 waves behind it
-  // instead of 4 (the f32 pass only: the f64 redo pass would spill at that size and handles a handful of tokens)
+  // instead of 4 (the f32 pass only: the f64 passes would spill at that size, and the redo pass handles a handful of tokens)
   constexpr int NTH = EB > 16 ? 512 : R16_THREADS;
   const size_t smem = router16_smem<NJ, LN, EB, 0>();
-  const int64_t tok_per_block = (NTH / 64) * 4;
-  int64_t need = (T + tok_per_block - 1) / tok_per_block;
+  const int64_t tok_per_block = (NTH / 64) * 4;  // (of the f32 pass; historical: it also sizes the 256-thread f64 passes' grid)
+  int64_t need = (a.T + tok_per_block - 1) / tok_per_block;
   // <= 768 workgroups (3 resident per CU; 512 = 2 per CU for the 16-expert image: the LDS weight image is loaded once
   // per workgroup), every workgroup the same number of 16-token groups
   constexpr int64_t max_wg = EB <= 8 ? 768 : (EB <= 16 ? 512 : 256);
   const int64_t iters = (need + max_wg - 1) / max_wg;
-  int grid = (int)(need < 1 ? 1 : (need + iters - 1) / (iters < 1 ? 1 : iters));
-  // with a chunk histogram every workgroup of the f32 pass walks ONE contiguous chunk of R16_HIST_TOK tokens
-  HistArgs ha{(EB == 8 && !(force_f64 & 1)) ? ln.hist : nullptr, R16_HIST_TOK};
-  const int grid0 = ha.hist ? (int)((T + R16_HIST_TOK - 1) / R16_HIST_TOK) : grid;
+  const int grid = (int)(need < 1 ? 1 : (need + iters - 1) / (iters < 1 ? 1 : iters));
+  // with a chunk histogram every workgroup of the f32 pass walks ONE contiguous chunk of R16_HIST_TOK tokens; an all-f64 run
+  // writes none (its f32 pass decides nothing), so it keeps the plain grid
+  const HistArgs ha{(EB == 8 && !a.all_f64) ? a.hist : nullptr, R16_HIST_TOK};
+  const int grid0 = ha.hist ? (int)((a.T + R16_HIST_TOK - 1) / R16_HIST_TOK) : grid;
+  const RouterPlan plan{grid0, grid, 16, LN, "smoe_router_topk/f32", "smoe_router_topk/f64", "smoe_router_topk/redo"};
   if (smem > 64 * 1024) {  // 16 experts x d 1024 (+ LayerNorm vectors): above the default dynamic-LDS limit
     SMOE_ENSURE_SMEM(router16_kernel<XT, NJ, 0, LN, NT, EB, 0, NTH>);
     SMOE_ENSURE_SMEM(router16_kernel<XT, NJ, 1, LN, NT, EB, 0, R16_THREADS>);
   }
-#define R16_LAUNCH(MODE, GRID, RC, RL)                                                                               \
-  hipLaunchKernelGGL((router16_kernel<XT, NJ, MODE, LN, NT, EB, 0, (MODE == 0 ? NTH : R16_THREADS)>), dim3(GRID),       \
-                     dim3(MODE == 0 ? NTH : R16_THREADS), smem, s, (const XT*)x,                                      \
-                     ln.g, ln.b, ln.eps, (NT*)ln.xn16, ln.xn32, wg, bg, noise, T, d, E, k, gate_kind, RC, RL, idx,   \
-                     score, logits_out, probs, SkipGateArgs{}, ha)
-  const bool ws_zero = (force_f64 & 2) != 0;
-  force_f64 &= 1;
-  if (force_f64 && !LN) {
-    R16_LAUNCH(1, grid, nullptr, nullptr);
-    SMOE_CHECK_LAUNCH("smoe_router_topk/f64");
-    return 0;
-  }
-  if (!ws_zero) {   // (a kept workspace is zero already: the redo pass clears its counter on the way out)
-    hipError_t me = smoe_zero_words(rc, 4, s);
-    if (me != hipSuccess) {
-      smoe_set_error("smoe_router_topk: counter clear failed: %s", hipGetErrorString(me));
-      return (int)me;
-    }
-  }
-  if (force_f64 && LN) {  // f64 mode still needs the normalised rows written: run the f32 pass for its stores first
-    R16_LAUNCH(0, grid, rc, rl);
-    SMOE_CHECK_LAUNCH("smoe_router_topk/f32");
-    R16_LAUNCH(1, grid, nullptr, nullptr);
-    SMOE_CHECK_LAUNCH("smoe_router_topk/f64");
-    return 0;
-  }
-  R16_LAUNCH(0, grid0, rc, rl);
-  SMOE_CHECK_LAUNCH("smoe_router_topk/f32");
-  R16_LAUNCH(1, (grid < 16 ? grid : 16), rc, rl);
-  SMOE_CHECK_LAUNCH("smoe_router_topk/redo");
+#define R16_LAUNCH(MODE, THREADS, g, rc, rl)                                                                                 \
+  hipLaunchKernelGGL((router16_kernel<XT, NJ, MODE, LN, NT, EB, 0, THREADS>), dim3(g), dim3(THREADS), smem, a.stream,        \
+                     (const XT*)a.x, a.ln_g, a.ln_b, a.ln_eps, (NT*)a.xn16, a.xn32, a.wg, a.bg, a.noise, a.T, a.d, a.E, a.k, \
+                     a.gate_kind, rc, rl, a.idx, a.score, a.logits, a.probs, a.gate, ha)
+  return run_router_passes(
+      a, plan, [&](int g, int32_t* rc, int32_t* rl) { R16_LAUNCH(0, NTH, g, rc, rl); },
+      [&](int g, int32_t* rc, int32_t* rl) { R16_LAUNCH(1, R16_THREADS, g, rc, rl); });
 #undef R16_LAUNCH
-  return 0;
 }
 
 // 16 / 32 experts on the f32 matrix cores (router_mt_kernel.h); SMOE_ROUTER_MT=0 keeps the 16-lanes-per-token kernel (A/B)
@@ -202,126 +172,85 @@ static bool use_router_mt() {
   static const bool on = [] { const char* v = getenv("SMOE_ROUTER_MT"); return !(v && v[0] == '0'); }();
   return on;
 }
+// SMOE_ROUTER_MT_HALVES=1 = the one-half form of the matrix-core f32 pass (A/B)
+static bool want_two_halves() {
+  static const bool on = [] { const char* v = getenv("SMOE_ROUTER_MT_HALVES"); return !(v && v[0] == '1'); }();
+  return on;
+}
 
-template <typename XT, int MP, bool LN, typename NT, int EB>
-int launch_mt(const void* x, const LnArgs& ln, const float* wg, const float* bg, const float* noise, int64_t T, int E, int k,
-              int gate_kind, int force_f64, int32_t* rc, int32_t* rl, int64_t* idx, float* score, float* logits_out,
-              float* probs, hipStream_t s) {
+template <typename XT, int MP, bool LN, typename NT, int EB> int launch_mt(const RouterArgs& a) {
   using namespace rmt;
-  constexpr size_t smem1 = router_mt_smem<MP, LN, EB, 1>();
-  static_assert(smem1 <= 160 * 1024, "router_mt: LDS image too large");
+  constexpr size_t smem = router_mt_smem<MP, LN, EB, 1>();
+  static_assert(smem <= 160 * 1024, "router_mt: LDS image too large");
   // An image that leaves room for ONE workgroup per CU (E = 32) runs the f32 pass on TWO four-wave halves per workgroup (HV = 2:
-  // two waves per SIMD on the same image; router_mt_kernel.h) when both halves' exchange areas fit; SMOE_ROUTER_MT_HALVES=1 = the
-  // one-half form (A/B).  The f64 re-do pass always runs one half.
-  constexpr bool can2 = 2 * smem1 > 160 * 1024 && router_mt_smem<MP, LN, EB, 2>() <= 160 * 1024;
-  static const bool want2 = [] { const char* v = getenv("SMOE_ROUTER_MT_HALVES"); return !(v && v[0] == '1'); }();
-  const bool two = can2 && want2;
-  const size_t smem = smem1;
-  const int64_t n_tiles = (T + 15) / 16;
+  // two waves per SIMD on the same image; router_mt_kernel.h) when both halves' exchange areas fit.  The f64 passes always run
+  // one half.
+  constexpr bool can2 = 2 * smem > 160 * 1024 && router_mt_smem<MP, LN, EB, 2>() <= 160 * 1024;
+  const bool two = can2 && want_two_halves();
+  const int64_t n_tiles = (a.T + 15) / 16;
   const int per_cu = (int)((160 * 1024) / smem) < 1 ? 1 : (int)((160 * 1024) / smem);
-  const int64_t max_wg = (int64_t)smoe_num_cus() * (per_cu > 2 ? 2 : per_cu);
-  // every workgroup the same number of tiles (the weight image is staged once per workgroup)
-  const int64_t iters = (n_tiles + max_wg - 1) / max_wg;
-  const int grid = (int)(n_tiles < 1 ? 1 : (n_tiles + iters - 1) / (iters < 1 ? 1 : iters));
+  // every workgroup the same number of tiles (the weight image is staged once per workgroup): `work` items over at most max_wg
+  auto even_grid = [](int64_t work, int64_t max_wg) {
+    const int64_t iters = (work + max_wg - 1) / max_wg;
+    return (int)(work < 1 ? 1 : (work + iters - 1) / (iters < 1 ? 1 : iters));
+  };
+  const int grid = even_grid(n_tiles, (int64_t)smoe_num_cus() * (per_cu > 2 ? 2 : per_cu));
+  // the f32 pass on two halves: half as many workgroups, each walking the tiles of two
+  const int grid_f32 = two ? even_grid((n_tiles + 1) / 2, smoe_num_cus()) : grid;
+  const RouterPlan plan{grid_f32, grid, 16, LN, "smoe_router_topk/mt f32", "smoe_router_topk/mt f64", "smoe_router_topk/mt redo"};
+  // always registered (historical: launch16 / launch_gate register above 64 KiB only; smoe_init pre-sets exactly this set)
   SMOE_ENSURE_SMEM(router_mt_kernel<XT, MP, 0, LN, NT, EB>);
   SMOE_ENSURE_SMEM(router_mt_kernel<XT, MP, 1, LN, NT, EB>);
-#define MT_LAUNCH(MODE, GRID, RC, RL)                                                                                  \
-  hipLaunchKernelGGL((router_mt_kernel<XT, MP, MODE, LN, NT, EB>), dim3(GRID), dim3(MT_THREADS), smem, s, (const XT*)x, \
-                     ln.g, ln.b, ln.eps, (NT*)ln.xn16, ln.xn32, wg, bg, noise, T, E, k, gate_kind, RC, RL, idx, score,  \
-                     logits_out, probs)
-  // the f32 pass on two halves: half as many workgroups, each walking the tiles of two
-  auto launch_f32 = [&](int32_t* RC, int32_t* RL) {
-    if constexpr (can2) {
-      if (two) {
-        constexpr size_t smem2 = router_mt_smem<MP, LN, EB, 2>();
-        const int64_t pairs = (n_tiles + 1) / 2, cap = smoe_num_cus();
-        const int64_t it2 = (pairs + cap - 1) / cap;
-        const int grid2 = (int)(pairs < 1 ? 1 : (pairs + it2 - 1) / (it2 < 1 ? 1 : it2));
-        hipLaunchKernelGGL((router_mt_kernel<XT, MP, 0, LN, NT, EB, 2>), dim3(grid2), dim3(2 * MT_THREADS), smem2, s, (const XT*)x,
-                           ln.g, ln.b, ln.eps, (NT*)ln.xn16, ln.xn32, wg, bg, noise, T, E, k, gate_kind, RC, RL, idx, score,
-                           logits_out, probs);
-        return;
-      }
-    }
-    MT_LAUNCH(0, grid, RC, RL);
-  };
   if constexpr (can2) SMOE_ENSURE_SMEM(router_mt_kernel<XT, MP, 0, LN, NT, EB, 2>);
-  const bool ws_zero = (force_f64 & 2) != 0;
-  force_f64 &= 1;
-  if (force_f64 && !LN) {
-    MT_LAUNCH(1, grid, nullptr, nullptr);
-    SMOE_CHECK_LAUNCH("smoe_router_topk/mt f64");
-    return 0;
-  }
-  if (!ws_zero) {
-    hipError_t me = smoe_zero_words(rc, 4, s);
-    if (me != hipSuccess) {
-      smoe_set_error("smoe_router_topk: counter clear failed: %s", hipGetErrorString(me));
-      return (int)me;
-    }
-  }
-  launch_f32(rc, rl);
-  SMOE_CHECK_LAUNCH("smoe_router_topk/mt f32");
-  if (force_f64) {   // f64 mode with LayerNorm: the f32 pass above wrote the normalised rows
-    MT_LAUNCH(1, grid, nullptr, nullptr);
-    SMOE_CHECK_LAUNCH("smoe_router_topk/mt f64");
-    return 0;
-  }
-  MT_LAUNCH(1, (grid < 16 ? grid : 16), rc, rl);
-  SMOE_CHECK_LAUNCH("smoe_router_topk/mt redo");
+#define MT_LAUNCH(MODE, HV, SMEM, g, rc, rl)                                                                                  \
+  hipLaunchKernelGGL((router_mt_kernel<XT, MP, MODE, LN, NT, EB, HV>), dim3(g), dim3(HV * MT_THREADS), SMEM, a.stream,        \
+                     (const XT*)a.x, a.ln_g, a.ln_b, a.ln_eps, (NT*)a.xn16, a.xn32, a.wg, a.bg, a.noise, a.T, a.E, a.k,       \
+                     a.gate_kind, rc, rl, a.idx, a.score, a.logits, a.probs)
+  return run_router_passes(
+      a, plan,
+      [&](int g, int32_t* rc, int32_t* rl) {
+        if constexpr (can2) {
+          if (two) {
+            MT_LAUNCH(0, 2, (router_mt_smem<MP, LN, EB, 2>()), g, rc, rl);
+            return;
+          }
+        }
+        MT_LAUNCH(0, 1, smem, g, rc, rl);
+      },
+      [&](int g, int32_t* rc, int32_t* rl) { MT_LAUNCH(1, 1, smem, g, rc, rl); });
 #undef MT_LAUNCH
-  return 0;
 }
 
-template <typename XT, bool LN, typename NT>
-int dispatch16(const void* x, const LnArgs& ln, const float* wg, const float* bg, const float* noise, int64_t T, int d,
-               int E, int k, int gate_kind, int f64, int32_t* rc, int32_t* rl, int64_t* idx, float* score, float* lo,
-               float* pr, hipStream_t s) {
+// -1 when the shape has no instantiation here
+template <typename XT, bool LN, typename NT> int dispatch16(const RouterArgs& a) {
+  const int d = a.d, E = a.E;
+#define R16_BY_D(LAUNCH, N768, N1024, EB)                   \
+  switch (d) {                                              \
+    case 768: return LAUNCH<XT, N768, LN, NT, EB>(a);       \
+    case 1024: return LAUNCH<XT, N1024, LN, NT, EB>(a);     \
+  }                                                         \
+  return -1
   if (E > 8 && use_router_mt()) {
-    if (E > 16) {
-      switch (d) {
-        case 768: return launch_mt<XT, 6, LN, NT, 32>(x, ln, wg, bg, noise, T, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-        case 1024: return launch_mt<XT, 8, LN, NT, 32>(x, ln, wg, bg, noise, T, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-      }
-    } else {
-      switch (d) {
-        case 768: return launch_mt<XT, 6, LN, NT, 16>(x, ln, wg, bg, noise, T, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-        case 1024: return launch_mt<XT, 8, LN, NT, 16>(x, ln, wg, bg, noise, T, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-      }
-    }
-    return -1;
+    if (E > 16) { R16_BY_D(launch_mt, 6, 8, 32); }
+    R16_BY_D(launch_mt, 6, 8, 16);
   }
-  if (E > 16) {  // 32 experts per lane (one workgroup per CU: the f32 weight image is 96-128 KB); ViT-B / ViT-L widths
-    switch (d) {
-      case 768: return launch16<XT, 12, LN, NT, 32>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-      case 1024: return launch16<XT, 16, LN, NT, 32>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-    }
-    return -1;
-  }
-  if (E > 8) {  // 16 experts per lane: instantiated for the ViT-B / ViT-L widths only (compile time)
-    switch (d) {
-      case 768: return launch16<XT, 12, LN, NT, 16>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-      case 1024: return launch16<XT, 16, LN, NT, 16>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-    }
-    return -1;
-  }
+  // 32 experts per lane: one workgroup per CU (the f32 weight image is 96-128 KB); 16 / 32 experts are instantiated for the
+  // ViT-B / ViT-L widths only (compile time)
+  if (E > 16) { R16_BY_D(launch16, 12, 16, 32); }
+  if (E > 8) { R16_BY_D(launch16, 12, 16, 16); }
   switch (d) {
-    case 192: return launch16<XT, 3, LN, NT, 8>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-    case 384: return launch16<XT, 6, LN, NT, 8>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-    case 768: return launch16<XT, 12, LN, NT, 8>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-    case 1024: return launch16<XT, 16, LN, NT, 8>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
+    case 192: return launch16<XT, 3, LN, NT, 8>(a);
+    case 384: return launch16<XT, 6, LN, NT, 8>(a);
   }
-  return -1;
+  R16_BY_D(launch16, 12, 16, 8);
+#undef R16_BY_D
 }
 
-template <typename XT>
-int dispatch16_ln(const void* x, const LnArgs& ln, const float* wg, const float* bg, const float* noise, int64_t T,
-                  int d, int E, int k, int gate_kind, int f64, int32_t* rc, int32_t* rl, int64_t* idx, float* score,
-                  float* lo, float* pr, hipStream_t s) {
-  if (!ln.on) return dispatch16<XT, false, f16>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-  if (ln.xn16_dtype == SMOE_BF16)
-    return dispatch16<XT, true, bf16_bits>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
-  return dispatch16<XT, true, f16>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, f64, rc, rl, idx, score, lo, pr, s);
+// LayerNorm off: NT is not looked at, one instantiation (f16) serves
+template <typename XT> int dispatch16_ln(const RouterArgs& a) {
+  if (!a.ln_on) return dispatch16<XT, false, f16>(a);
+  if (a.xn16_dtype == SMOE_BF16) return dispatch16<XT, true, bf16_bits>(a);
+  return dispatch16<XT, true, f16>(a);
 }
 
 }  // namespace
@@ -333,17 +262,9 @@ static bool shape_ok16(int d, int E, int k) {
 }
 
 // returns -1 when the shape is not covered by this fast path (caller falls back to router.hip)
-int smoe_router16_try(const void* x, int x_dtype, const float* wg, const float* bg, const float* noise, int64_t T,
-                      int d, int E, int k, int gate_kind, int force_f64, int32_t* rc, int32_t* rl, int64_t* idx,
-                      float* score, float* logits_out, float* probs, hipStream_t s) {
-  if (!shape_ok16(d, E, k)) return -1;
-  LnArgs ln{nullptr, nullptr, 0.f, nullptr, SMOE_F16, nullptr, false};
-  switch (x_dtype) {
-    case SMOE_F32: return dispatch16_ln<float>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-    case SMOE_F16: return dispatch16_ln<f16>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-    case SMOE_BF16: return dispatch16_ln<bf16_bits>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-  }
-  return -1;
+int smoe_router16_try(const RouterArgs& a) {
+  if (!shape_ok16(a.d, a.E, a.k)) return -1;
+  return router_by_x_dtype(a, [&](auto xt) { return dispatch16_ln<decltype(xt)>(a); });
 }
 
 extern "C" int smoe_ln_router_supported(int d, int E, int k) { return shape_ok16(d, E, k) ? 1 : 0; }
@@ -362,29 +283,25 @@ extern "C" int smoe_ln_router_topk(const void* x, int x_dtype, const float* ln_g
                                    const float* noise, int64_t T, int d, int E, int k, int gate_kind, int64_t* idx,
                                    float* score, float* logits_out, float* probs, int32_t* chunk_hist, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  const int force_f64 = ((gate_kind & 0x100) ? 1 : 0) | ((gate_kind & 0x200) ? 2 : 0);   // bit 1: the workspace's counter words are kept zero by the caller
-  gate_kind &= 0xff;
+  RouterArgs a{};
+  a.entry = "smoe_ln_router_topk";
+  a.x = x, a.x_dtype = x_dtype;
+  a.ln_on = true, a.ln_g = ln_gamma, a.ln_b = ln_beta, a.ln_eps = ln_eps, a.xn16 = xn16, a.xn16_dtype = xn16_dtype, a.xn32 = xn32;
+  a.wg = wg, a.bg = bg, a.noise = noise;
+  a.T = T, a.d = d, a.E = E, a.k = k;
+  a.idx = idx, a.score = score, a.logits = logits_out, a.probs = probs;
+  a.stream = (hipStream_t)stream;
+  router_decode_gate_kind(a, gate_kind);
   if (T == 0) return 0;
   SMOE_REQUIRE(x && wg && idx && score, "smoe_ln_router_topk: null pointer");
   SMOE_REQUIRE(shape_ok16(d, E, k), "smoe_ln_router_topk: unsupported shape d=%d E=%d k=%d", d, E, k);
   SMOE_REQUIRE(T >= 0 && T < (1ll << 31), "smoe_ln_router_topk: bad T");
   SMOE_REQUIRE(k >= 1 && k <= E, "smoe_ln_router_topk: bad k");
-  SMOE_REQUIRE(gate_kind == SMOE_GATE_NAIVE || (gate_kind == SMOE_GATE_SWITCH && k == 1), "smoe_ln_router_topk: bad gate");
+  SMOE_REQUIRE(a.gate_kind == SMOE_GATE_NAIVE || (a.gate_kind == SMOE_GATE_SWITCH && k == 1), "smoe_ln_router_topk: bad gate");
   SMOE_REQUIRE(xn16_dtype == SMOE_F16 || xn16_dtype == SMOE_BF16, "smoe_ln_router_topk: xn16 must be f16 or bf16");
-  SMOE_REQUIRE(workspace && workspace_bytes >= 16 + (((size_t)T * 4 + 15) & ~(size_t)15), "smoe_ln_router_topk: workspace too small");
-  if (T == 0) return 0;
-  int32_t* rc = reinterpret_cast<int32_t*>(workspace);
-  int32_t* rl = reinterpret_cast<int32_t*>((char*)workspace + 16);
-  LnArgs ln{ln_gamma, ln_beta, ln_eps, xn16, xn16_dtype, xn32, true};
-  ln.hist = (chunk_hist && smoe_router_chunk_hist_tokens(d, E, k)) ? chunk_hist : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  switch (x_dtype) {
-    case SMOE_F32: return dispatch16_ln<float>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-    case SMOE_F16: return dispatch16_ln<f16>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-    case SMOE_BF16: return dispatch16_ln<bf16_bits>(x, ln, wg, bg, noise, T, d, E, k, gate_kind, force_f64, rc, rl, idx, score, logits_out, probs, s);
-  }
-  smoe_set_error("smoe_ln_router_topk: bad x_dtype %d", x_dtype);
-  return 1;
+  if (int rc = router_take_workspace(a, workspace, workspace_bytes)) return rc;
+  a.hist = (chunk_hist && smoe_router_chunk_hist_tokens(d, E, k)) ? chunk_hist : nullptr;
+  return router_by_x_dtype(a, [&](auto xt) { return dispatch16_ln<decltype(xt)>(a); });
 }
 
 // LayerNorm over the last dimension, d in {192, 384, 768, 1024}; out dtype f32 / f16 / bf16.

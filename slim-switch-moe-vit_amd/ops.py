@@ -105,7 +105,19 @@ def _chk(t: torch.Tensor, name: str, dtype=None, ndim=None, align: int = 16):
 
 
 _router_ws = {}   # (device index, stream) -> uint8 workspace whose counter words are zero between calls
-WS_KEPT_ZERO = 0x200   # gate_kind flag (router entry points) / with_ln bit 1 (smoe_gate_ln_router): "the counter words are zero"
+# gate_kind flags of smoe_router_topk / smoe_ln_router_topk (include/slimmoe.h: SMOE_ROUTER_ALL_F64, SMOE_ROUTER_WS_KEPT_ZERO)
+ALL_F64 = 0x100        # every token through the f64 pass (test mode)
+WS_KEPT_ZERO = 0x200   # "the workspace's counter words are zero": no clearing launch
+GATE_WITH_LN, GATE_WS_KEPT_ZERO = 1, 2   # the bits of smoe_gate_ln_router's with_ln
+
+
+def _router_call_workspace(dev: torch.device, T: int, all_f64: bool = False):
+    """(workspace, its size in bytes, gate_kind flag bits) for one call of a router entry point."""
+    ws_bytes = _lib.load().smoe_router_workspace_bytes(T)
+    if all_f64:
+        # (the all-f64 test mode runs its f32 pass without a redo pass behind it: it gets a scratch workspace and the clearing launch)
+        return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes, ALL_F64
+    return _router_workspace(dev, ws_bytes), ws_bytes, WS_KEPT_ZERO
 
 
 def _router_workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
@@ -143,12 +155,10 @@ def router_topk(x: torch.Tensor, wg: torch.Tensor, bg: Optional[torch.Tensor], k
     logits = torch.empty((T, E), dtype=torch.float32, device=x.device) if want_logits else None
     probs = torch.empty((T, E), dtype=torch.float32, device=x.device) if want_probs else None
     lib = _lib.load()
-    ws_bytes = lib.smoe_router_workspace_bytes(T)
-    # (the all-f64 test mode runs its f32 pass without a redo pass behind it: it gets a scratch workspace and the clearing launch)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if force_f64 else _router_workspace(x.device, ws_bytes)
+    ws, ws_bytes, flags = _router_call_workspace(x.device, T, force_f64)
     with _timed("router", {"bytes": T * d * x.element_size()}, x):
         rc = lib.smoe_router_topk(_ptr(x), dtype_code(x.dtype), _ptr(wg), _ptr(bg), _ptr(noise), T, d, E, k,
-                                  gate_kind | (0x100 if force_f64 else WS_KEPT_ZERO), _ptr(idx), _ptr(score), _ptr(logits),
+                                  gate_kind | flags, _ptr(idx), _ptr(score), _ptr(logits),
                                   _ptr(probs), _ptr(ws), ws_bytes, _stream(x))
     _lib.check(rc, "smoe_router_topk")
     return idx, score, logits, probs
@@ -356,13 +366,12 @@ def ln_router_topk(x: torch.Tensor, ln_weight: Optional[torch.Tensor], ln_bias: 
     logits = torch.empty((T, E), dtype=torch.float32, device=dev) if want_logits else None
     probs = torch.empty((T, E), dtype=torch.float32, device=dev) if want_probs else None
     lib = _lib.load()
-    ws_bytes = lib.smoe_router_workspace_bytes(T)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if force_f64 else _router_workspace(dev, ws_bytes)
+    ws, ws_bytes, flags = _router_call_workspace(dev, T, force_f64)
     nbytes = T * d * (x.element_size() + (2 if xn16 is not None else 0) + (4 if want_xn32 else 0))
     with _timed("ln_router", {"bytes": nbytes}, x):
         rc = lib.smoe_ln_router_topk(_ptr(x), dtype_code(x.dtype), _ptr(ln_weight), _ptr(ln_bias), float(eps), _ptr(xn16),
                                      dtype_code(xn16_dtype) if xn16_dtype is not None else F16, _ptr(xn32), _ptr(wg),
-                                     _ptr(bg), _ptr(noise), T, d, E, k, gate_kind | (0x100 if force_f64 else WS_KEPT_ZERO),
+                                     _ptr(bg), _ptr(noise), T, d, E, k, gate_kind | flags,
                                      _ptr(idx), _ptr(score), _ptr(logits), _ptr(probs), _ptr(None if force_f64 else hist), _ptr(ws),
                                      ws_bytes, _stream(x))
     _lib.check(rc, "smoe_ln_router_topk")
@@ -422,11 +431,11 @@ def gate_ln_router(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch
     if skip_count is not None:
         _chk(skip_count, "skip_count", torch.int32, align=4)
     lib = _lib.load()
-    ws_bytes = lib.smoe_router_workspace_bytes(T)
-    ws = _router_workspace(dev, ws_bytes)
+    ws, ws_bytes, flags = _router_call_workspace(dev, T)
+    with_ln = (GATE_WITH_LN if ln is not None else 0) | (GATE_WS_KEPT_ZERO if flags & WS_KEPT_ZERO else 0)
     nbytes = T * d * (4 + (2 if xn16 is not None else 0) + (4 if xn32 is not None else 0) + (4 if tk32 is not None else 0))
     with _timed("gate_ln_router" if E else "gate_ln", {"bytes": nbytes}, x):
-        rc = lib.smoe_gate_ln_router(_ptr(x), F32, (1 if ln is not None else 0) | 2, _ptr(lg), _ptr(lb), float(eps), _ptr(gw),
+        rc = lib.smoe_gate_ln_router(_ptr(x), F32, with_ln, _ptr(lg), _ptr(lb), float(eps), _ptr(gw),
                                      _ptr(gb), _ptr(thr), _ptr(xn16),
                                      dtype_code(xn16_dtype) if xn16_dtype is not None else F16, _ptr(xn32),
                                      _ptr(zero_out), _ptr(wg), _ptr(bg), T, d, E, k, _ptr(idx), _ptr(idx_plan),

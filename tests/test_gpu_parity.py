@@ -168,6 +168,123 @@ def test_router_switch_matches_oracle(with_noise):
     assert torch.allclose(probs.cpu(), o_p, rtol=0, atol=5e-6)
 
 
+# The pass sequence of the router entry points (counter clear -> f32 pass -> f64 redo pass, or f64 over all tokens), pinned where
+# the other tests do not reach: LayerNorm + forced f64, the kept workspace's invariant, and the clearing launch a plain C caller gets.
+@pytest.mark.parametrize("T,d,E,k", [(333, 192, 4, 2),      # 16-lanes-per-token kernel
+                                     (333, 768, 16, 2),     # matrix-core kernel
+                                     (333, 768, 32, 1)])    # matrix-core kernel, f32 pass on two halves
+def test_ln_router_forced_f64_writes_the_same_rows_and_routes_like_the_oracle(T, d, E, k):
+    """Forced f64 with LayerNorm: the f32 pass still runs for its stores (xn16 / xn32 bit-equal to the normal call's), then every
+    token goes through the f64 pass: idx and logits are the oracle's on the rows the kernel wrote."""
+    g = _gen(T + d + E)
+    x = torch.randn(T, d, generator=g)
+    lw, lb = 1 + 0.1 * torch.randn(d, generator=g), 0.1 * torch.randn(d, generator=g)
+    wg = torch.randn(E, d, generator=g) * 0.05
+    bg = torch.randn(E, generator=g) * 0.1
+    dev = [t.to(DEV) for t in (x, lw, lb)] + [1e-6] + [t.to(DEV) for t in (wg, bg)]
+    n16, n32, _, _, _, _ = ops.ln_router_topk(*dev, k, ops.GATE_NAIVE, want_xn32=True, want_logits=True, force_f64=False)
+    xn16, xn32, idx, score, logits, _ = ops.ln_router_topk(*dev, k, ops.GATE_NAIVE, want_xn32=True, want_logits=True, force_f64=True)
+    assert torch.equal(xn32, n32) and torch.equal(xn16, n16), "the normalised rows do not depend on the routing mode"
+    o_idx, o_score, o_logits = mo.naive_gate(xn32.cpu(), wg, bg, k)
+    assert torch.equal(idx.cpu(), o_idx), "routing indices must be bit-exact"
+    assert torch.equal(logits.cpu(), o_logits), "f64-accumulated logits round to the same f32"
+    assert torch.allclose(score.cpu(), o_score, rtol=0, atol=5e-6)
+
+
+_PASS_CASES = [("router", 64, 3), ("router", 192, 4), ("router", 768, 16), ("ln_router", 192, 4), ("ln_router", 768, 16),
+               ("gate_router", 192, 4), ("gate", 192, 0)]   # generic, 16-lane, matrix-core launcher; gate + router, gate only
+
+
+def _tie_planted(entry, d, E):
+    """T = 512 inputs (on the device) whose redo list is not empty: the planted exact and near ties of
+    test_router_near_ties_take_the_f64_path_and_match_the_oracle, and for the skip gate rows that sit on its threshold."""
+    T = 512
+    g = _gen(21 + d + E)
+    x = torch.randn(T, d, generator=g)
+    t = {"T": T, "k": min(2, max(E, 1))}
+    if E:
+        wg = torch.randn(E, d, generator=g) * 0.02
+        wg[E - 1] = wg[0]                                    # exact tie on every token
+        src, near = (0, 1) if E == 3 else (1, E - 2)
+        wg[near] = wg[src]; wg[near, 17] += 3e-9             # near tie far below the f32 accumulation error
+        t["wg"], t["bg"] = wg.to(DEV), torch.zeros(E, device=DEV)
+    if entry != "router":
+        lw, lb = 1 + 0.1 * torch.randn(d, generator=g), 0.1 * torch.randn(d, generator=g)
+        t["lw"], t["lb"] = lw.to(DEV), lb.to(DEV)
+    if entry.startswith("gate"):
+        # gate logit z = rstd <x - mean, lw gw> + <lb, gw> + gb.  Every fifth row loses its component along the centred lw gw, and
+        # gb = -<lb, gw>: z ~ 0 = logit(threshold 0.5) up to rounding, far inside the f32 pass' error bound; zero rows likewise
+        gw = torch.randn(d, generator=g) * 0.1
+        g2 = (lw * gw).double()
+        g2c = g2 - g2.mean()
+        xc = x[::5].double() - x[::5].double().mean(1, keepdim=True)
+        x[::5] = (x[::5].double() - ((xc @ g2) / (g2c @ g2c))[:, None] * g2c).float()
+        x[::7] = 0.0
+        gb = -(lb.double() @ gw.double()).float().reshape(1)
+        t["gw"], t["gb"], t["thr"] = gw.to(DEV), gb.to(DEV), torch.tensor(0.5, device=DEV)
+    t["x"] = x.to(DEV)
+    return t
+
+
+def _pass_call(entry, t):
+    """The ops call of one case; its outputs as a list of tensors."""
+    if entry == "router":
+        return [o for o in ops.router_topk(t["x"], t["wg"], t["bg"], t["k"], ops.GATE_NAIVE, want_logits=True) if o is not None]
+    if entry == "ln_router":
+        r = ops.ln_router_topk(t["x"], t["lw"], t["lb"], 1e-6, t["wg"], t["bg"], t["k"], ops.GATE_NAIVE, want_xn32=True, want_logits=True)
+        return [o for o in r if o is not None]
+    r = ops.gate_ln_router(t["x"], t["gw"], t["gb"], t["thr"], ln=(t["lw"], t["lb"], 1e-6), wg=t.get("wg"), bg=t.get("bg"), k=t["k"],
+                           xn16_dtype=torch.float16, want_xn32=True, want_mask=True)
+    return [r[n] for n in ("xn16", "xn32", "idx", "idx_plan", "score", "mask") if r[n] is not None]
+
+
+@pytest.mark.parametrize("entry,d,E", _PASS_CASES)
+def test_router_calls_leave_the_kept_workspace_counters_zero(entry, d, E):
+    """Every redo pass leaves both counter words of the kept workspace zero (ops._router_workspace relies on it in every forward):
+    checked after each call on inputs with a non-empty redo list, and a second identical call returns the same bits."""
+    t = _tie_planted(entry, d, E)
+    ws = ops._router_workspace(torch.device(DEV), 1)
+    assert ws is ops._router_ws[(0, ops._stream(t["x"]))]
+    redo_list = ws[16:16 + 4 * t["T"]].view(torch.int32)
+    redo_list.fill_(-1)                                      # (the list part carries no state between calls)
+    first = _pass_call(entry, t)
+    assert (redo_list >= 0).any(), "the planted ties must put tokens on the redo list, or the checks below are vacuous"
+    assert not ws[:16].any(), ws[:16].tolist()
+    second = _pass_call(entry, t)
+    assert not ws[:16].any(), ws[:16].tolist()
+    assert len(first) == len(second) and all(torch.equal(u, v) for u, v in zip(first, second))
+
+
+@pytest.mark.parametrize("entry,d,E", _PASS_CASES)
+def test_router_library_calls_clear_a_dirty_workspace_themselves(entry, d, E):
+    """What a plain C caller gets: a private workspace full of 0xFF and no "kept zero" flag -> the call clears the counter words
+    itself; every output bit-equal to the ops call's (kept workspace, no clearing launch), the counter words zero afterwards."""
+    from slim_switch_moe_vit_amd import _lib
+    t = _tie_planted(entry, d, E)
+    want = _pass_call(entry, t)
+    got = [torch.empty_like(o) for o in want]
+    lib, p, x, T, k = _lib.load(), ops._ptr, t["x"], t["T"], t["k"]
+    ws_bytes = lib.smoe_router_workspace_bytes(T)
+    ws = torch.full((ws_bytes,), 0xFF, dtype=torch.uint8, device=DEV)
+    if entry == "router":
+        idx, score, logits = got
+        rc = lib.smoe_router_topk(p(x), ops.F32, p(t["wg"]), p(t["bg"]), None, T, d, E, k, ops.GATE_NAIVE, p(idx), p(score), p(logits),
+                                  None, p(ws), ws_bytes, ops._stream(x))
+    elif entry == "ln_router":
+        xn16, xn32, idx, score, logits = got
+        rc = lib.smoe_ln_router_topk(p(x), ops.F32, p(t["lw"]), p(t["lb"]), 1e-6, p(xn16), ops.F16, p(xn32), p(t["wg"]), p(t["bg"]), None,
+                                     T, d, E, k, ops.GATE_NAIVE, p(idx), p(score), p(logits), None, None, p(ws), ws_bytes, ops._stream(x))
+    else:
+        xn16, xn32, mask = got[0], got[1], got[-1]
+        idx, idx_plan, score = got[2:5] if E else (None, None, None)
+        rc = lib.smoe_gate_ln_router(p(x), ops.F32, 1, p(t["lw"]), p(t["lb"]), 1e-6, p(t["gw"]), p(t["gb"]), p(t["thr"]), p(xn16), ops.F16,
+                                     p(xn32), None, p(t.get("wg")), p(t.get("bg")), T, d, E, k, p(idx), p(idx_plan), p(score), p(mask),
+                                     None, None, None, p(ws), ws_bytes, ops._stream(x))
+    assert rc == 0, lib.smoe_last_error()
+    assert not ws[:16].any(), ws[:16].tolist()
+    assert all(torch.equal(u, v) for u, v in zip(got, want))
+
+
 # ------------------------------------------------------------------------------------------ plan
 @pytest.mark.parametrize("n,E,cap", [(1, 4, -1), (63, 4, -1), (1024, 8, -1), (1025, 8, -1), (50432, 8, -1),
                                      (50432, 8, 6304), (20000, 32, 100), (5000, 300, -1), (4096, 1, -1),
