@@ -636,6 +636,30 @@ int smoe_distill_fwd(const void* student, int s_dtype, const void* teacher, int 
 int smoe_distill_bwd(const void* student, int s_dtype, const void* teacher, int t_dtype, int mode, float tau, float alpha, int64_t B,
                      int C, const double* row_stats, const int32_t* row_label, const float* g, void* dlogits, void* stream);
 
+/* ---- binary cross-entropy with logits (main.py:663-664 `criterion = torch.nn.BCEWithLogitsLoss()` under --bce-loss; engine.py:49-50
+ * `targets = targets.gt(0.0).type(targets.dtype)`) ------------------------------------------------------------------------------------
+ * logits [B, C] (f32 / f16 / bf16, computed in f32), target f32 [B, C].  binarize != 0: every target is read as t' = (t > 0 ? 1 : 0) --
+ * engine.py:50's strict `> 0`: -0.0, 0.0, a negative value and NaN give 0; binarize == 0: t' = t.
+ * smoe_bce_fwd : element loss = max(x, 0) - x t' + log1p(exp(-|x|)) (torch's stable form), in f32.  row_loss f32 [B] = the row's sum:
+ *                one workgroup per row, the f32 elements added in double on a fixed tree and rounded once.  *loss = (sum of row_loss in
+ *                a fixed order, in double) * 1 / (B C), rounded once to f32: reduction='mean', the only one the reference constructs.
+ *                The same bits run to run; a row's loss does not depend on the other rows.  Two launches.
+ * smoe_bce_bwd : dlogits [B, C] (the logits' dtype, rounded once from f32) = *g (sigmoid(x) - t') / (B C); g is a DEVICE f32 scalar
+ *                (the gradient of the mean loss: it carries the loss scale).  sigmoid(x) - t' is formed from e = exp(-|x|) as
+ *                (1 - t') - e / (1 + e) for x >= 0 and e / (1 + e) - t' for x < 0: nothing overflows, and 1 - sigmoid keeps its
+ *                precision for large x.  Purely element-wise.  One launch.
+ * Non-finite inputs: an element whose logit is NaN or infinite, or whose (unbinarized) target is, gives a non-finite row_loss for its
+ * row and a non-finite *loss; which of inf / NaN appears is not preserved (torch's own formula gives NaN for x = +inf, t = 1).
+ * dlogits[b, c] depends on logits[b, c], target[b, c] and *g only: a NaN or infinite logit makes its own gradient element NaN and
+ * touches no other; other rows' row_loss keep their bits.
+ * B <= 65535 (one workgroup per row / grid row), 0 < C <= 2^30.  16-byte accesses when C % 8 == 0 and logits, target (and dlogits) are
+ * 16-byte aligned, element-wise otherwise.  B == 0 returns 0 at once; all arguments (null pointers, dtype code, sizes, alignment of
+ * the f32 buffers) are checked before any launch; no allocation, no synchronisation, no atomics: both can be captured.             */
+int smoe_bce_fwd(const void* logits, int dtype, const float* target, int binarize, int64_t B, int C, float* row_loss, float* loss,
+                 void* stream);
+int smoe_bce_bwd(const void* logits, int dtype, const float* target, int binarize, int64_t B, int C, const float* g, void* dlogits,
+                 void* stream);
+
 /* ---- small helpers ------------------------------------------------------------------------------------
  * elementwise cast between dtypes (weight shadow copies; not on the per-step path)                  */
 int smoe_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);

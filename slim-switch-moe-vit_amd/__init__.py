@@ -10,6 +10,6 @@ from .resmoe import *  # noqa: F401,F403
 from .engine import evaluate, accuracy, EvalMeter, train_one_epoch, GraphedForward, GraphedTrainStep  # noqa: F401
 from .optim import AdamW, ModelEma, NativeScaler, invalidate_weight_images  # noqa: F401
 from .mixup import Mixup  # noqa: F401
-from .loss import SoftTargetCrossEntropy, LabelSmoothingCrossEntropy, DistillationLoss  # noqa: F401
+from .loss import SoftTargetCrossEntropy, LabelSmoothingCrossEntropy, DistillationLoss, BCEWithLogitsLoss  # noqa: F401
 
 __version__ = "0.1.0"

@@ -119,6 +119,8 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "smoe_distill_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int64, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "smoe_bce_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "smoe_bce_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "smoe_unique_id_bytes": (c_int, []),
     "smoe_unique_id": (c_int, [c_void_p]),
     "smoe_ctx_create": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

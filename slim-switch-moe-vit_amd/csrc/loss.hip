@@ -11,6 +11,9 @@
 //   smoe_distill_fwd  : the distillation term between the student's distillation logits and a teacher's logits -- soft: KL(teacher ||
 //                       student) at temperature tau; hard: cross-entropy against the teacher's argmax -- and its blend with the base loss
 //   smoe_distill_bwd  : its gradient for the student's distillation logits (the teacher gets none)
+// and the criterion of --bce-loss (main.py:663-664 torch.nn.BCEWithLogitsLoss, with engine.py:49-50's `targets.gt(0.0)` folded in):
+//   smoe_bce_fwd      : mean over all elements of max(x, 0) - x t + log1p(exp(-|x|)); a row sum per workgroup + a fixed-order mean
+//   smoe_bce_bwd      : dlogits = g (sigmoid(x) - t) / (B C) in the logits' dtype, element-wise
 // and what the reference's evaluate() computes after every forward (engine.py:99-113):
 //   smoe_eval_metrics : per-row cross-entropy + the label's rank in one pass, then the batch's loss / top-k accuracies and an f64
 //                       accumulator for the epoch, all on the device (upstream: a dozen launches and three host reads)
@@ -704,6 +707,115 @@ void launch_distill_bwd(bool vec, dim3 grid, hipStream_t s, const void* student,
     default: CALL(bf16_bits, bf16_bits); break;                                                     \
   }
 
+// ---- binary cross-entropy with logits (main.py:663-664 torch.nn.BCEWithLogitsLoss; engine.py:49-50 the target rewrite) ---------------
+// the target an element is scored against: engine.py:50's `targets.gt(0.0)` when binarize (-0.0, a negative value and NaN give 0)
+__device__ __forceinline__ float bce_target(float t, bool binarize) { return binarize ? (t > 0.f ? 1.f : 0.f) : t; }
+
+// torch's stable form max(x, 0) - x t + log1p(exp(-|x|)).  fmaxf drops a NaN logit, x * t keeps it (NaN * 0 = NaN); an infinite logit
+// gives inf or NaN (-inf * 0, inf - inf) under every target: a non-finite logit never gives a finite element.
+__device__ __forceinline__ float bce_elem(float x, float t) { return (fmaxf(x, 0.f) - x * t) + log1pf(expf(-fabsf(x))); }
+
+// One workgroup per row: soft_ce_fwd_kernel's loads (8 consecutive elements per lane when VEC, element-wise otherwise) and its tree
+// (wave butterfly, then (w0 + w1) + (w2 + w3)).  The elements are f32; their sum runs in double, so that row_loss is the sum of the
+// f32 elements rounded once, whatever C is (a row of 1000 elements near 200 would otherwise lose ~log2(C) bits to the running sum).
+template <typename T, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void bce_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, int binarize,
+                                                               int C, float* __restrict__ row_loss) {
+  __shared__ double red[LOSS_THREADS / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const T* __restrict__ x = logits + (size_t)row * C;
+  const float* __restrict__ t = target + (size_t)row * C;
+  const bool bin = binarize != 0;
+  double acc = 0.0;
+  const int span = LOSS_THREADS * CE_K;
+  for (int c0 = 0; c0 < C; c0 += span) {
+    if constexpr (VEC) {     // C % 8 == 0 and aligned bases: 8 consecutive logits and targets per lane
+      const int c = c0 + tid * CE_K;
+      if (c < C) {
+        float v[CE_K], tv[CE_K];
+        load8(x + c, v);
+        load8(t + c, tv);
+#pragma unroll
+        for (int q = 0; q < CE_K; ++q) acc += (double)bce_elem(v[q], bce_target(tv[q], bin));
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < CE_K; ++q) {
+        const int c = c0 + q * LOSS_THREADS + tid;
+        if (c < C) acc += (double)bce_elem(to_f32<T>(x[c]), bce_target(t[c], bin));
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) row_loss[row] = (float)((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// *loss = (sum of row_loss in a fixed order, in double) / (B C), rounded once: reduction='mean' over every element
+__global__ __launch_bounds__(LOSS_THREADS) void bce_mean_kernel(const float* __restrict__ row_loss, int B, int C, float* __restrict__ loss) {
+  __shared__ double red[LOSS_THREADS / 64];
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < B; r += LOSS_THREADS) acc += (double)row_loss[r];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *loss = (float)(((red[0] + red[1]) + (red[2] + red[3])) * (1.0 / ((double)B * (double)C)));
+}
+
+// sigmoid(x) - t from e = exp(-|x|) in (0, 1]: x >= 0: (1 - t) - e / (1 + e); x < 0: e / (1 + e) - t.  Nothing overflows, and under
+// t = 1 a large x gives -e / (1 + e) itself, not 1 - 1.  A NaN or infinite logit, whose loss element is not finite, gives NaN.
+__device__ __forceinline__ float bce_grad(float x, float t, float scale) {
+  const float e = expf(-fabsf(x));
+  const float r = e / (1.0f + e);
+  const float d = x >= 0.f ? (1.0f - t) - r : r - t;
+  return fabsf(x) <= 3.4028234664e38f ? d * scale : __builtin_nanf("");
+}
+
+// purely element-wise: dlogits[b, c] reads logits[b, c], target[b, c] and *g only
+template <typename T, bool VEC>
+__global__ __launch_bounds__(LOSS_THREADS) void bce_bwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, int binarize,
+                                                               int B, int C, const float* __restrict__ g, T* __restrict__ dlogits) {
+  const size_t at = (size_t)blockIdx.y * C;
+  const bool bin = binarize != 0;
+  const float scale = (float)((double)*g / ((double)B * (double)C));
+  if constexpr (VEC) {
+    const int c = (blockIdx.x * LOSS_THREADS + threadIdx.x) * CE_K;
+    if (c >= C) return;
+    float v[CE_K], tv[CE_K], o[CE_K];
+    load8(logits + at + c, v);
+    load8(target + at + c, tv);
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) o[q] = bce_grad(v[q], bce_target(tv[q], bin), scale);
+    store8(dlogits + at + c, o);
+  } else {
+#pragma unroll
+    for (int q = 0; q < CE_K; ++q) {
+      const int c = blockIdx.x * (LOSS_THREADS * CE_K) + q * LOSS_THREADS + threadIdx.x;
+      if (c >= C) continue;
+      dlogits[at + c] = from_f32<T>(bce_grad(to_f32<T>(logits[at + c]), bce_target(target[at + c], bin), scale));
+    }
+  }
+}
+
+template <typename T>
+void launch_bce_fwd(bool vec, int B, hipStream_t s, const void* logits, const float* target, int binarize, int C, float* row_loss) {
+  if (vec) hipLaunchKernelGGL((bce_fwd_kernel<T, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, C, row_loss);
+  else hipLaunchKernelGGL((bce_fwd_kernel<T, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, C, row_loss);
+}
+
+template <typename T>
+void launch_bce_bwd(bool vec, dim3 grid, hipStream_t s, const void* logits, const float* target, int binarize, int B, int C, const float* g,
+                    void* dlogits) {
+  if (vec) hipLaunchKernelGGL((bce_bwd_kernel<T, true>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, B, C, g, (T*)dlogits);
+  else hipLaunchKernelGGL((bce_bwd_kernel<T, false>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, B, C, g, (T*)dlogits);
+}
+
+// element size of a dtype code (the logits' own alignment)
+inline uintptr_t bce_elem_mask(int dtype) { return dtype == SMOE_F32 ? 3 : 1; }
+
 }  // namespace
 
 extern "C" int smoe_mixup_images(float* x, int64_t B, int C, int H, int W, const float* lam, const float* one_minus,
@@ -838,5 +950,46 @@ extern "C" int smoe_distill_bwd(const void* student, int s_dtype, const void* te
   DISTILL_PAIRS(DB)
 #undef DB
   SMOE_CHECK_LAUNCH("smoe_distill_bwd");
+  return 0;
+}
+
+extern "C" int smoe_bce_fwd(const void* logits, int dtype, const float* target, int binarize, int64_t B, int C, float* row_loss, float* loss,
+                            void* stream) {
+  SMOE_REQUIRE(smoe_dtype_ok(dtype), "smoe_bce_fwd: bad dtype code %d", dtype);
+  SMOE_REQUIRE(B >= 0 && B <= GRID_Y_MAX && C > 0 && C <= (1 << 30), "smoe_bce_fwd: bad sizes (B <= 65535, 0 < C <= 2^30)");
+  if (B == 0) return 0;
+  SMOE_REQUIRE(logits && target && row_loss && loss, "smoe_bce_fwd: null pointer");
+  SMOE_REQUIRE(((uintptr_t)logits & bce_elem_mask(dtype)) == 0 && (((uintptr_t)target | (uintptr_t)row_loss | (uintptr_t)loss) & 3) == 0,
+               "smoe_bce_fwd: misaligned pointer (logits to its element size, the f32 buffers to 4 bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(logits, target, nullptr, C);
+  switch (dtype) {
+    case SMOE_F32: launch_bce_fwd<float>(vec, (int)B, s, logits, target, binarize, C, row_loss); break;
+    case SMOE_F16: launch_bce_fwd<f16>(vec, (int)B, s, logits, target, binarize, C, row_loss); break;
+    default: launch_bce_fwd<bf16_bits>(vec, (int)B, s, logits, target, binarize, C, row_loss); break;
+  }
+  SMOE_CHECK_LAUNCH("smoe_bce_fwd");
+  hipLaunchKernelGGL(bce_mean_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_loss, (int)B, C, loss);
+  SMOE_CHECK_LAUNCH("smoe_bce_fwd (mean)");
+  return 0;
+}
+
+extern "C" int smoe_bce_bwd(const void* logits, int dtype, const float* target, int binarize, int64_t B, int C, const float* g, void* dlogits,
+                            void* stream) {
+  SMOE_REQUIRE(smoe_dtype_ok(dtype), "smoe_bce_bwd: bad dtype code %d", dtype);
+  SMOE_REQUIRE(B >= 0 && B <= GRID_Y_MAX && C > 0 && C <= (1 << 30), "smoe_bce_bwd: bad sizes (B <= 65535, 0 < C <= 2^30)");
+  if (B == 0) return 0;
+  SMOE_REQUIRE(logits && target && g && dlogits, "smoe_bce_bwd: null pointer");
+  SMOE_REQUIRE((((uintptr_t)logits | (uintptr_t)dlogits) & bce_elem_mask(dtype)) == 0 && (((uintptr_t)target | (uintptr_t)g) & 3) == 0,
+               "smoe_bce_bwd: misaligned pointer (logits and dlogits to their element size, the f32 buffers to 4 bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = ce_vec_ok(logits, target, dlogits, C);
+  const dim3 grid((unsigned)((C + LOSS_THREADS * CE_K - 1) / (LOSS_THREADS * CE_K)), (unsigned)B);
+  switch (dtype) {
+    case SMOE_F32: launch_bce_bwd<float>(vec, grid, s, logits, target, binarize, (int)B, C, g, dlogits); break;
+    case SMOE_F16: launch_bce_bwd<f16>(vec, grid, s, logits, target, binarize, (int)B, C, g, dlogits); break;
+    default: launch_bce_bwd<bf16_bits>(vec, grid, s, logits, target, binarize, (int)B, C, g, dlogits); break;
+  }
+  SMOE_CHECK_LAUNCH("smoe_bce_bwd");
   return 0;
 }

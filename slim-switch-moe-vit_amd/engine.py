@@ -497,6 +497,15 @@ def _criterion_takes_inputs(criterion) -> bool:
     return len(params) >= 3
 
 
+def _criterion_binarizes(criterion) -> bool:
+    """Whether the criterion -- or a ``DistillationLoss``'s base criterion -- is this package's ``BCEWithLogitsLoss(binarize=True)``,
+    which scores every target as ``target > 0`` itself: engine.py:49-50's ``targets.gt(0.0).type(targets.dtype)`` is then left out."""
+    from .loss import BCEWithLogitsLoss, DistillationLoss
+    if isinstance(criterion, DistillationLoss):
+        criterion = criterion.base_criterion
+    return isinstance(criterion, BCEWithLogitsLoss) and criterion.binarize
+
+
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tuple[torch.Tensor, torch.Tensor]],
                     optimizer: torch.optim.Optimizer, device, epoch: int, loss_scaler, max_norm=None, model_ema=None,
                     mixup_fn=None, set_training_mode=True, args=None, *, aux_loss_weight: float = 0.0, gate_delta=None,
@@ -506,7 +515,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
     positions 9 and 10): autocast forward, criterion, ``loss_scaler(loss, optimizer, clip_grad=max_norm,
     parameters=model.parameters())`` (optim.NativeScaler keeps the whole step on the device), ``model_ema.update(model)``
     after every step (``optim.ModelEma``: one launch, captured with the step under ``hip_graph``) and ``mixup_fn(samples,
-    targets)`` before it when given, ``args.bce_loss`` as at engine.py:49-50.
+    targets)`` before it when given, ``args.bce_loss`` as at engine.py:49-50 (the ``gt`` line is left to a ``loss.BCEWithLogitsLoss(
+    binarize=True)``, bare or as a ``DistillationLoss``'s base criterion, which applies it inside its kernels).
     ``max_norm=None`` = no clipping (what main.py passes by default, ``--clip-grad None``).  A criterion whose forward takes
     three tensors is called like the reference's DistillationLoss, ``criterion(samples, outputs, targets)``.
 
@@ -544,6 +554,8 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable[Tup
     if every_step:
         check_every = 1
     bce = bool(getattr(args, "bce_loss", False)) if args is not None else False
+    if bce and _criterion_binarizes(criterion):
+        bce = False      # loss.BCEWithLogitsLoss(binarize=True) applies engine.py:50's `> 0` to the same values inside its kernels
     loss_sum, bad, n = torch.zeros((), device=dev), torch.zeros((), device=dev), 0
     graphed = None
     ep_graph = hip_graph is True or _ep_world_size(model) == 1      # (captured RCCL between distinct GPUs: only on request so far)

@@ -1,4 +1,4 @@
-"""The reference's training criteria (main.py:653-661): ``timm.loss.SoftTargetCrossEntropy`` when Mixup / CutMix is on (targets are
+"""The reference's training criteria (main.py:653-664): ``timm.loss.SoftTargetCrossEntropy`` when Mixup / CutMix is on (targets are
 dense rows), ``timm.loss.LabelSmoothingCrossEntropy`` when it is off and ``--smoothing`` > 0; engine.py:54 calls them in every step.
 
 timm is not installed where this package is developed or run: the two modules restate timm 0.4.12's ``timm/loss/cross_entropy.py``
@@ -14,6 +14,11 @@ criterion on the class-token logits, blended with a distillation term between th
 logits go through one ``torch.autograd.Function`` over ``smoe_distill_fwd`` / ``smoe_distill_bwd`` -- two launches forward, one backward
 (upstream: two log-softmaxes, two divisions, kl_div, sum, two scalings and the blend, and their backward); everything else takes the
 reference's torch lines.
+
+``BCEWithLogitsLoss`` is the criterion of ``--bce-loss`` (main.py:663-664 ``torch.nn.BCEWithLogitsLoss()``), a subclass with the upstream
+constructor.  CUDA logits go through one ``torch.autograd.Function`` over ``smoe_bce_fwd`` / ``smoe_bce_bwd`` -- two launches forward, one
+backward; with ``binarize=True`` the kernels also apply engine.py:49-50's ``targets.gt(0.0)``, and ``engine.train_one_epoch`` leaves
+that line (a [B, C] intermediate and two launches) out.  ``weight`` / ``pos_weight`` / other reductions take torch's line.
 """
 from __future__ import annotations
 
@@ -155,3 +160,50 @@ class DistillationLoss(nn.Module):
                 and _logits_ok(teacher) and teacher.shape == kd.shape and teacher.device == kd.device and not teacher.requires_grad
                 and base_loss.dim() == 0 and base_loss.device == kd.device and base_loss.is_floating_point()
                 and isinstance(self.tau, (int, float)) and self.tau > 0 and isinstance(self.alpha, (int, float)))
+
+
+class _BCEWithLogits(torch.autograd.Function):
+    """mean over all elements of the binary cross-entropy between ``logits`` and f32 ``target`` (read as ``target > 0`` when
+    ``binarize``) on smoe_bce_fwd / smoe_bce_bwd."""
+
+    @staticmethod
+    def forward(ctx, logits, target, binarize: bool):
+        loss, _ = ops.bce_fwd(logits, target, binarize)
+        ctx.save_for_backward(logits, target)
+        ctx.binarize = binarize
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target = ctx.saved_tensors
+        if g.dtype != torch.float32:
+            g = g.float()
+        return ops.bce_bwd(logits, target, g.contiguous(), ctx.binarize), None, None
+
+
+class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
+    """``torch.nn.BCEWithLogitsLoss`` (main.py:663-664, ``--bce-loss``) with one keyword-only extension: ``binarize=True`` scores every
+    target as ``target > 0`` -- engine.py:49-50's ``targets = targets.gt(0.0).type(targets.dtype)`` without the intermediate tensor
+    (``train_one_epoch`` then leaves that line out).  CUDA logits with a floating-point target of their shape that needs no gradient,
+    no ``weight`` / ``pos_weight`` and ``reduction='mean'`` go through the kernels: two launches forward, one backward; the loss is
+    an f32 scalar.  Anything else takes torch's line (after the ``gt`` line when ``binarize``)."""
+
+    def __init__(self, weight=None, size_average=None, reduce=None, reduction: str = 'mean', pos_weight=None, *,
+                 binarize: bool = False):
+        super().__init__(weight, size_average, reduce, reduction, pos_weight)
+        self.binarize = bool(binarize)
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        x = input
+        if (self.weight is None and self.pos_weight is None and self.reduction == 'mean' and _logits_ok(x)
+                and target.shape == x.shape and target.device == x.device and target.is_floating_point() and not target.requires_grad):
+            C = x.shape[-1]
+            t = target.detach().reshape(-1, C)
+            if t.dtype != torch.float32:      # (binarized in its own dtype: a positive f64 target may round to 0 in f32)
+                t = (t.gt(0.0) if self.binarize else t).float()
+            if not t.is_contiguous() or t.data_ptr() % 4:
+                t = t.contiguous()
+            return _BCEWithLogits.apply(x.reshape(-1, C), t, self.binarize)
+        if self.binarize:
+            target = target.gt(0.0).type(target.dtype)
+        return F.binary_cross_entropy_with_logits(input, target, self.weight, pos_weight=self.pos_weight, reduction=self.reduction)

@@ -1460,3 +1460,41 @@ def distill_bwd(student: torch.Tensor, teacher: torch.Tensor, stats: torch.Tenso
                                       float(alpha), B, C, _ptr(stats), _ptr(labels), _ptr(g), _ptr(out), _stream(student))
     _lib.check(rc, "smoe_distill_bwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------- binary cross-entropy with logits
+def _bce_args(logits, target):
+    _chk(logits, "logits", ndim=2, align=2)
+    dtype_code(logits.dtype)
+    _chk(target, "target", torch.float32, 2, align=4)
+    if target.shape != logits.shape or target.device != logits.device:
+        raise RuntimeError("bce: target must be f32 [B, C] on the logits' device")
+    return logits.shape[0], logits.shape[1]
+
+
+def bce_fwd(logits: torch.Tensor, target: torch.Tensor, binarize: bool = False):
+    """``torch.nn.BCEWithLogitsLoss()`` (reduction 'mean') on the device in two launches (smoe_bce_fwd): ``logits`` f32 / f16 / bf16
+    [B, C], ``target`` f32 [B, C]; ``binarize``: every target counts as ``target > 0`` (engine.py:49-50).  -> (loss f32 [], row_loss
+    f32 [B] = each row's sum of element losses)."""
+    B, C = _bce_args(logits, target)
+    row_loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    with _timed("bce_fwd", {"bytes": B * C * (logits.element_size() + 4)}, logits):
+        rc = _lib.load().smoe_bce_fwd(_ptr(logits), dtype_code(logits.dtype), _ptr(target), int(bool(binarize)), B, C, _ptr(row_loss),
+                                      _ptr(loss), _stream(logits))
+    _lib.check(rc, "smoe_bce_fwd")
+    return loss, row_loss
+
+
+def bce_bwd(logits: torch.Tensor, target: torch.Tensor, g: torch.Tensor, binarize: bool = False) -> torch.Tensor:
+    """dlogits = g (sigmoid(x) - t) / (B C) in the logits' dtype (smoe_bce_bwd); ``g``: device f32 scalar."""
+    B, C = _bce_args(logits, target)
+    _chk(g, "g", torch.float32, align=4)
+    if g.numel() != 1 or g.device != logits.device:
+        raise RuntimeError("bce_bwd: a device f32 scalar g expected")
+    out = torch.empty_like(logits)
+    with _timed("bce_bwd", {"bytes": B * C * (2 * logits.element_size() + 4)}, logits):
+        rc = _lib.load().smoe_bce_bwd(_ptr(logits), dtype_code(logits.dtype), _ptr(target), int(bool(binarize)), B, C, _ptr(g), _ptr(out),
+                                      _stream(logits))
+    _lib.check(rc, "smoe_bce_bwd")
+    return out
