@@ -17,6 +17,8 @@
 // and what the reference's evaluate() computes after every forward (engine.py:99-113):
 //   smoe_eval_metrics : per-row cross-entropy + the label's rank in one pass, then the batch's loss / top-k accuracies and an f64
 //                       accumulator for the epoch, all on the device (upstream: a dozen launches and three host reads)
+// Shared by the criteria: wave_sum / tree4 and MaxSum's tree4 (the block reduction's two halves), MaxSumD::merge, and with_dtype /
+// with_vec (from dtype codes and alignment to a kernel instantiation).  DESIGN.md, "The loss family's shared pieces".
 #include "smoe_common.h"
 #include <type_traits>
 
@@ -157,6 +159,25 @@ struct MaxSum {
 };
 
 constexpr int CE_K = 8;     // logits per thread and step
+constexpr int NW = LOSS_THREADS / 64;     // waves of a workgroup
+
+// THE sum of a value (f32, f64, int) over the workgroup, in two halves around the caller's one __syncthreads(): wave_sum over the
+// wave, lane 0 of each wave stores it to red[wave], the barrier, then tree4(red) = (w0 + w1) + (w2 + w3) on whoever needs it.
+// Neither half synchronises: a kernel that reduces several values stores them all and synchronises once.
+template <typename V> __device__ __forceinline__ V wave_sum(V v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+template <typename V> __device__ __forceinline__ V tree4(const V (&red)[NW]) { return (red[0] + red[1]) + (red[2] + red[3]); }
+// ... and MaxSum's second half, over the waves' (m, s) as they lie in LDS: the same pairing, (w0, w1), (w2, w3), then the two
+__device__ __forceinline__ MaxSum tree4(const float (&rm)[NW], const float (&rs)[NW]) {
+  MaxSum a{rm[0], rs[0]}, b{rm[2], rs[2]};
+  a.merge(rm[1], rs[1]);
+  b.merge(rm[3], rs[3]);
+  a.merge(b.m, b.s);
+  return a;
+}
 
 // compensated (Kahan) sum: a row's targets are one or two values near 1 among thousands near smoothing / C, and the row loss multiplies
 // their sum by the log-sum-exp -- a plain running sum's rounding (up to C / 256 half-ulps of 1 per thread) would show there
@@ -192,7 +213,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void soft_ce_fwd_kernel(const T* __re
                                                                    const int64_t* __restrict__ labels, float smoothing, int C,
                                                                    float* __restrict__ row_loss, float* __restrict__ row_max,
                                                                    float* __restrict__ row_logsum, float* __restrict__ row_tsum) {
-  __shared__ float red[4][LOSS_THREADS / 64];
+  __shared__ float red[4][NW];
   const int row = blockIdx.x, tid = threadIdx.x;
   const T* __restrict__ x = logits + (size_t)row * C;
   const float* __restrict__ t = target ? target + (size_t)row * C : nullptr;
@@ -239,12 +260,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void soft_ce_fwd_kernel(const T* __re
   if ((tid & 63) == 0) { red[0][tid >> 6] = ms.m; red[1][tid >> 6] = ms.s; red[2][tid >> 6] = dot; red[3][tid >> 6] = ts; }
   __syncthreads();
   if (tid == 0) {
-    MaxSum a{red[0][0], red[1][0]}, b{red[0][2], red[1][2]};
-    a.merge(red[0][1], red[1][1]);
-    b.merge(red[0][3], red[1][3]);
-    a.merge(b.m, b.s);
-    dot = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-    ts = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+    const MaxSum a = tree4(red[0], red[1]);
+    dot = tree4(red[2]);
+    ts = tree4(red[3]);
     float ls = logf(a.s);
     float lse = a.m + ls;
     if (!(fabsf(lse) <= 3.4028234664e38f)) lse = ls = __builtin_nanf("");
@@ -263,16 +281,15 @@ __global__ __launch_bounds__(LOSS_THREADS) void soft_ce_fwd_kernel(const T* __re
   }
 }
 
-// *loss = (sum of row_loss in a fixed order) / B: one workgroup, the same tree whatever ran before
+// *loss = (sum of row_loss in a fixed order) / B: one workgroup, strided partial sums into wave_sum / tree4 whatever ran before
 __global__ __launch_bounds__(LOSS_THREADS) void row_mean_kernel(const float* __restrict__ row_loss, int B, float* __restrict__ loss) {
-  __shared__ float red[LOSS_THREADS / 64];
+  __shared__ float red[NW];
   float acc = 0.f;
   for (int r = threadIdx.x; r < B; r += LOSS_THREADS) acc += row_loss[r];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) *loss = ((red[0] + red[1]) + (red[2] + red[3])) / (float)B;
+  if (threadIdx.x == 0) *loss = tree4(red) / (float)B;
 }
 
 template <typename T, bool VEC>
@@ -309,20 +326,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void soft_ce_bwd_kernel(const T* __re
   }
 }
 
-template <typename T>
-void launch_ce_fwd(bool vec, int B, hipStream_t s, const void* logits, const float* target, const int64_t* labels, float smoothing, int C,
-                   float* row_loss, float* row_max, float* row_logsum, float* row_tsum) {
-  if (vec) hipLaunchKernelGGL((soft_ce_fwd_kernel<T, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum);
-  else hipLaunchKernelGGL((soft_ce_fwd_kernel<T, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum);
-}
-
-template <typename T>
-void launch_ce_bwd(bool vec, dim3 grid, hipStream_t s, const void* logits, const float* target, const int64_t* labels, float smoothing,
-                   int B, int C, const float* row_max, const float* row_logsum, const float* row_tsum, const float* g, void* dlogits) {
-  if (vec) hipLaunchKernelGGL((soft_ce_bwd_kernel<T, true>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, B, C, row_max, row_logsum, row_tsum, g, (T*)dlogits);
-  else hipLaunchKernelGGL((soft_ce_bwd_kernel<T, false>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing, B, C, row_max, row_logsum, row_tsum, g, (T*)dlogits);
-}
-
 // 8 consecutive elements per lane need 16-byte aligned rows of every operand
 bool ce_vec_ok(const void* logits, const void* target, const void* dlogits, int C) {
   return C % CE_K == 0 && (((uintptr_t)logits | (uintptr_t)target | (uintptr_t)dlogits) & 15) == 0;
@@ -334,15 +337,16 @@ constexpr int GRID_Y_MAX = 65535;
 constexpr int EVAL_MAX_K = 4;
 struct TopK { int k[EVAL_MAX_K]; };
 
-// One workgroup per row: soft_ce_fwd_kernel's label form at smoothing 0 -- the same loads per thread, the same ce_step and the same
-// tree, so row_loss has its bits -- and, on the registers that pass holds anyway, the label's rank: the number of classes that come
+// One workgroup per row: soft_ce_fwd_kernel's label form at smoothing 0 -- its loads per thread and its butterfly (written out in
+// both kernels: keep them alike), its ce_step and MaxSum's tree4, so row_loss has its bits -- and, on the registers that pass
+// holds anyway, the label's rank: the number of classes that come
 // before it in a stable descending order where a NaN is the largest value (torch.topk's order; ties go to the lower index).  The
 // label's logit x_t is one uniform load up front.  A label outside [0, C): nothing is loaded for it, rank INT32_MAX, loss NaN.
 template <typename T, bool VEC>
 __global__ __launch_bounds__(LOSS_THREADS) void eval_row_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels, int C,
                                                                 float* __restrict__ row_loss, int32_t* __restrict__ row_rank) {
-  __shared__ float red[2][LOSS_THREADS / 64];
-  __shared__ int redc[LOSS_THREADS / 64];
+  __shared__ float red[2][NW];
+  __shared__ int redc[NW];
   const int row = blockIdx.x, tid = threadIdx.x;
   const T* __restrict__ x = logits + (size_t)row * C;
   const int64_t l = labels[row];
@@ -389,18 +393,16 @@ __global__ __launch_bounds__(LOSS_THREADS) void eval_row_kernel(const T* __restr
   if ((tid & 63) == 0) { red[0][tid >> 6] = ms.m; red[1][tid >> 6] = ms.s; redc[tid >> 6] = cnt; }
   __syncthreads();
   if (tid == 0) {
-    MaxSum a{red[0][0], red[1][0]}, b{red[0][2], red[1][2]};
-    a.merge(red[0][1], red[1][1]);
-    b.merge(red[0][3], red[1][3]);
-    a.merge(b.m, b.s);
+    const MaxSum a = tree4(red[0], red[1]);
     float lse = a.m + logf(a.s);
     if (!(fabsf(lse) <= 3.4028234664e38f)) lse = __builtin_nanf("");
     row_loss[row] = valid ? lse - xt : __builtin_nanf("");
-    row_rank[row] = valid ? (redc[0] + redc[1]) + (redc[2] + redc[3]) : 0x7fffffff;
+    row_rank[row] = valid ? tree4(redc) : 0x7fffffff;
   }
 }
 
-// One workgroup: batch[0] = the mean of row_loss on row_mean_kernel's tree (its bits); batch[1 + i] = (count_i * 100) * f32(1 / B) with
+// One workgroup: batch[0] = the mean of row_loss as row_mean_kernel forms it (the same strided partial sums, butterfly and tree4:
+// its bits); batch[1 + i] = (count_i * 100) * f32(1 / B) with
 // count_i = #{rows : rank < k_i} -- the f32 operations torch runs ON THE DEVICE for timm's `correct.float().sum() * 100.0 / B` (a
 // division by a host scalar is a multiplication by its reciprocal there; measured: a true division differs in 65 of 193 counts at
 // B = 192); acc (may be NULL) f64 [2 + nk] +=
@@ -409,7 +411,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void eval_row_kernel(const T* __restr
 __global__ __launch_bounds__(LOSS_THREADS) void eval_batch_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_rank,
                                                                   int B, TopK ks, int nk, float* __restrict__ batch,
                                                                   double* __restrict__ acc) {
-  constexpr int NW = LOSS_THREADS / 64;
   __shared__ float redf[NW];
   __shared__ double redd[NW];
   __shared__ int redc[EVAL_MAX_K][NW];
@@ -440,24 +441,18 @@ __global__ __launch_bounds__(LOSS_THREADS) void eval_batch_kernel(const float* _
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    batch[0] = ((redf[0] + redf[1]) + (redf[2] + redf[3])) / (float)B;
+    batch[0] = tree4(redf) / (float)B;
     const float inv_b = (float)(1.0 / (double)B);      // torch divides a device tensor by a host scalar as x * f32(1 / B)
     if (acc) {
-      acc[0] += (redd[0] + redd[1]) + (redd[2] + redd[3]);
+      acc[0] += tree4(redd);
       acc[1] += (double)B;
     }
     for (int i = 0; i < nk; ++i) {
-      const int n = (redc[i][0] + redc[i][1]) + (redc[i][2] + redc[i][3]);
+      const int n = tree4(redc[i]);
       batch[1 + i] = __fmul_rn(__fmul_rn((float)n, 100.f), inv_b);
       if (acc) acc[2 + i] += (double)n;
     }
   }
-}
-
-template <typename T>
-void launch_eval_row(bool vec, int B, hipStream_t s, const void* logits, const int64_t* labels, int C, float* row_loss, int32_t* row_rank) {
-  if (vec) hipLaunchKernelGGL((eval_row_kernel<T, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, labels, C, row_loss, row_rank);
-  else hipLaunchKernelGGL((eval_row_kernel<T, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, labels, C, row_loss, row_rank);
 }
 
 // ---- distillation (losses.py:53-72) -----------------------------------------------------------------------------------------
@@ -481,6 +476,20 @@ struct MaxSumD {
   float m;
   double s;
   __device__ __forceinline__ double factor(float mm, double itau) const { return m == mm ? 1.0 : exp(((double)m - (double)mm) * itau); }
+  // takes in another partial (m2, s2) ...
+  __device__ __forceinline__ void merge(float m2, double s2, double itau) {
+    const float mm = fmaxf(m, m2);
+    s = s * factor(mm, itau) + s2 * MaxSumD{m2, 0.0}.factor(mm, itau);
+    m = mm;
+  }
+  // ... and with it a second pair of sums (acc, a2) that rides on the same maximum
+  __device__ __forceinline__ void merge(float m2, double s2, double& acc, double a2, double itau) {
+    const float mm = fmaxf(m, m2);
+    const double f1 = factor(mm, itau), f2 = MaxSumD{m2, 0.0}.factor(mm, itau);
+    s = s * f1 + s2 * f2;
+    acc = acc * f1 + a2 * f2;
+    m = mm;
+  }
 };
 
 // K logits of a thread: ce_step in double.  acc (teacher rows only, with the student's logits in sv): sum of exp((t - max) / tau)
@@ -517,7 +526,6 @@ template <typename TS, typename TT, bool VEC>
 __global__ __launch_bounds__(LOSS_THREADS) void distill_fwd_kernel(const TS* __restrict__ student, const TT* __restrict__ teacher, int mode,
                                                                    float tau, int B, int C, double* __restrict__ row_val,
                                                                    double* __restrict__ stats, int32_t* __restrict__ label) {
-  constexpr int NW = LOSS_THREADS / 64;
   __shared__ double redd[3][NW];
   __shared__ float redf[3][NW];
   __shared__ int redi[NW];
@@ -557,25 +565,13 @@ __global__ __launch_bounds__(LOSS_THREADS) void distill_fwd_kernel(const TS* __r
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
-    {
-      const float m2 = __shfl_xor(ms.m, m, 64);
-      const double s2 = __shfl_xor(ms.s, m, 64);
-      const float mm = fmaxf(ms.m, m2);
-      ms.s = ms.s * ms.factor(mm, itau) + s2 * MaxSumD{m2, 0.0}.factor(mm, itau);
-      ms.m = mm;
-    }
+    ms.merge(__shfl_xor(ms.m, m, 64), __shfl_xor(ms.s, m, 64), itau);
     if (hard) {
       const float v2 = __shfl_xor(bv, m, 64);
       const int i2 = __shfl_xor(bi, m, 64);
       if (argmax_takes(v2, i2, bv, bi)) { bv = v2; bi = i2; }
     } else {
-      const float m2 = __shfl_xor(mt.m, m, 64);
-      const double s2 = __shfl_xor(mt.s, m, 64), a2 = __shfl_xor(acc, m, 64);
-      const float mm = fmaxf(mt.m, m2);
-      const double f1 = mt.factor(mm, itau), f2 = MaxSumD{m2, 0.0}.factor(mm, itau);
-      mt.s = mt.s * f1 + s2 * f2;
-      acc = acc * f1 + a2 * f2;
-      mt.m = mm;
+      mt.merge(__shfl_xor(mt.m, m, 64), __shfl_xor(mt.s, m, 64), acc, __shfl_xor(acc, m, 64), itau);
     }
   }
   const int w = tid >> 6;
@@ -587,17 +583,14 @@ __global__ __launch_bounds__(LOSS_THREADS) void distill_fwd_kernel(const TS* __r
     MaxSumD a{redf[0][0], redd[0][0]}, t{redf[1][0], redd[1][0]};
     acc = redd[2][0]; bv = redf[2][0]; bi = redi[0];
     for (int k = 1; k < NW; ++k) {
+      // (a.merge(redf[0][k], redd[0][k], itau), written out: the form that keeps this loop's LDS reads as they are)
       const float mm = fmaxf(a.m, redf[0][k]);
       a.s = a.s * a.factor(mm, itau) + redd[0][k] * MaxSumD{redf[0][k], 0.0}.factor(mm, itau);
       a.m = mm;
       if (hard) {
         if (argmax_takes(redf[2][k], redi[k], bv, bi)) { bv = redf[2][k]; bi = redi[k]; }
       } else {
-        const float tm = fmaxf(t.m, redf[1][k]);
-        const double f1 = t.factor(tm, itau), f2 = MaxSumD{redf[1][k], 0.0}.factor(tm, itau);
-        t.s = t.s * f1 + redd[1][k] * f2;
-        acc = acc * f1 + redd[2][k] * f2;
-        t.m = tm;
+        t.merge(redf[1][k], redd[1][k], acc, redd[2][k], itau);
       }
     }
     const double nan = __builtin_nan("");
@@ -625,15 +618,14 @@ __global__ __launch_bounds__(LOSS_THREADS) void distill_fwd_kernel(const TS* __r
 __global__ __launch_bounds__(LOSS_THREADS) void distill_blend_kernel(const double* __restrict__ row_val, int B, int C, int mode, float tau,
                                                                      float alpha, const float* __restrict__ base,
                                                                      float* __restrict__ distill, float* __restrict__ loss) {
-  __shared__ double red[LOSS_THREADS / 64];
+  __shared__ double red[NW];
   double acc = 0.0;
   for (int r = threadIdx.x; r < B; r += LOSS_THREADS) acc += row_val[r];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double sum = (red[0] + red[1]) + (red[2] + red[3]);
+    const double sum = tree4(red);
     const double d = mode == DISTILL_HARD ? sum / (double)B : sum * ((double)tau * (double)tau) / ((double)B * (double)C);
     *distill = (float)d;
     *loss = (float)((double)*base * (1.0 - (double)alpha) + d * (double)alpha);
@@ -679,34 +671,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void distill_bwd_kernel(const TS* __r
   }
 }
 
-template <typename TS, typename TT>
-void launch_distill_fwd(bool vec, hipStream_t s, const void* student, const void* teacher, int mode, float tau, int B, int C, double* row_val,
-                        double* stats, int32_t* label) {
-  if (vec) hipLaunchKernelGGL((distill_fwd_kernel<TS, TT, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, B, C, row_val, stats, label);
-  else hipLaunchKernelGGL((distill_fwd_kernel<TS, TT, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, B, C, row_val, stats, label);
-}
-
-template <typename TS, typename TT>
-void launch_distill_bwd(bool vec, dim3 grid, hipStream_t s, const void* student, const void* teacher, int mode, float tau, float alpha, int B,
-                        int C, const double* stats, const int32_t* label, const float* g, void* dlogits) {
-  if (vec) hipLaunchKernelGGL((distill_bwd_kernel<TS, TT, true>), grid, dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, alpha, B, C, stats, label, g, (TS*)dlogits);
-  else hipLaunchKernelGGL((distill_bwd_kernel<TS, TT, false>), grid, dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher, mode, tau, alpha, B, C, stats, label, g, (TS*)dlogits);
-}
-
-// the nine (student, teacher) dtype pairs
-#define DISTILL_PAIRS(CALL)                                                                          \
-  switch (s_dtype * 3 + t_dtype) {                                                                  \
-    case SMOE_F32 * 3 + SMOE_F32: CALL(float, float); break;                                        \
-    case SMOE_F32 * 3 + SMOE_F16: CALL(float, f16); break;                                          \
-    case SMOE_F32 * 3 + SMOE_BF16: CALL(float, bf16_bits); break;                                   \
-    case SMOE_F16 * 3 + SMOE_F32: CALL(f16, float); break;                                          \
-    case SMOE_F16 * 3 + SMOE_F16: CALL(f16, f16); break;                                            \
-    case SMOE_F16 * 3 + SMOE_BF16: CALL(f16, bf16_bits); break;                                     \
-    case SMOE_BF16 * 3 + SMOE_F32: CALL(bf16_bits, float); break;                                   \
-    case SMOE_BF16 * 3 + SMOE_F16: CALL(bf16_bits, f16); break;                                     \
-    default: CALL(bf16_bits, bf16_bits); break;                                                     \
-  }
-
 // ---- binary cross-entropy with logits (main.py:663-664 torch.nn.BCEWithLogitsLoss; engine.py:49-50 the target rewrite) ---------------
 // the target an element is scored against: engine.py:50's `targets.gt(0.0)` when binarize (-0.0, a negative value and NaN give 0)
 __device__ __forceinline__ float bce_target(float t, bool binarize) { return binarize ? (t > 0.f ? 1.f : 0.f) : t; }
@@ -715,13 +679,13 @@ __device__ __forceinline__ float bce_target(float t, bool binarize) { return bin
 // gives inf or NaN (-inf * 0, inf - inf) under every target: a non-finite logit never gives a finite element.
 __device__ __forceinline__ float bce_elem(float x, float t) { return (fmaxf(x, 0.f) - x * t) + log1pf(expf(-fabsf(x))); }
 
-// One workgroup per row: soft_ce_fwd_kernel's loads (8 consecutive elements per lane when VEC, element-wise otherwise) and its tree
-// (wave butterfly, then (w0 + w1) + (w2 + w3)).  The elements are f32; their sum runs in double, so that row_loss is the sum of the
+// One workgroup per row: soft_ce_fwd_kernel's columns per thread (8 consecutive elements per lane when VEC, every 256th otherwise),
+// the row's sum over the workgroup on wave_sum / tree4.  The elements are f32; their sum runs in double, so that row_loss is the sum of the
 // f32 elements rounded once, whatever C is (a row of 1000 elements near 200 would otherwise lose ~log2(C) bits to the running sum).
 template <typename T, bool VEC>
 __global__ __launch_bounds__(LOSS_THREADS) void bce_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, int binarize,
                                                                int C, float* __restrict__ row_loss) {
-  __shared__ double red[LOSS_THREADS / 64];
+  __shared__ double red[NW];
   const int row = blockIdx.x, tid = threadIdx.x;
   const T* __restrict__ x = logits + (size_t)row * C;
   const float* __restrict__ t = target + (size_t)row * C;
@@ -746,23 +710,21 @@ __global__ __launch_bounds__(LOSS_THREADS) void bce_fwd_kernel(const T* __restri
       }
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  acc = wave_sum(acc);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
   __syncthreads();
-  if (tid == 0) row_loss[row] = (float)((red[0] + red[1]) + (red[2] + red[3]));
+  if (tid == 0) row_loss[row] = (float)tree4(red);
 }
 
 // *loss = (sum of row_loss in a fixed order, in double) / (B C), rounded once: reduction='mean' over every element
 __global__ __launch_bounds__(LOSS_THREADS) void bce_mean_kernel(const float* __restrict__ row_loss, int B, int C, float* __restrict__ loss) {
-  __shared__ double red[LOSS_THREADS / 64];
+  __shared__ double red[NW];
   double acc = 0.0;
   for (int r = threadIdx.x; r < B; r += LOSS_THREADS) acc += (double)row_loss[r];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) *loss = (float)(((red[0] + red[1]) + (red[2] + red[3])) * (1.0 / ((double)B * (double)C)));
+  if (threadIdx.x == 0) *loss = (float)(tree4(red) * (1.0 / ((double)B * (double)C)));
 }
 
 // sigmoid(x) - t from e = exp(-|x|) in (0, 1]: x >= 0: (1 - t) - e / (1 + e); x < 0: e / (1 + e) - t.  Nothing overflows, and under
@@ -800,21 +762,20 @@ __global__ __launch_bounds__(LOSS_THREADS) void bce_bwd_kernel(const T* __restri
   }
 }
 
-template <typename T>
-void launch_bce_fwd(bool vec, int B, hipStream_t s, const void* logits, const float* target, int binarize, int C, float* row_loss) {
-  if (vec) hipLaunchKernelGGL((bce_fwd_kernel<T, true>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, C, row_loss);
-  else hipLaunchKernelGGL((bce_fwd_kernel<T, false>), dim3(B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, C, row_loss);
+// ---- launch dispatch: the element type(s) and VEC of an instantiation from the run-time dtype code(s) and alignment -----------------
+// f(tag) with tag a TagF32 / TagF16 / TagBF16 (tag.T is the element type); the entry points have checked the code
+template <typename F> void with_dtype(int code, F f) {
+  switch (code) {
+    case SMOE_F32: f(TagF32{}); break;
+    case SMOE_F16: f(TagF16{}); break;
+    default: f(TagBF16{}); break;
+  }
 }
-
-template <typename T>
-void launch_bce_bwd(bool vec, dim3 grid, hipStream_t s, const void* logits, const float* target, int binarize, int B, int C, const float* g,
-                    void* dlogits) {
-  if (vec) hipLaunchKernelGGL((bce_bwd_kernel<T, true>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, B, C, g, (T*)dlogits);
-  else hipLaunchKernelGGL((bce_bwd_kernel<T, false>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, B, C, g, (T*)dlogits);
+// f(v) with v a std::true_type / std::false_type (v.value is VEC)
+template <typename F> void with_vec(bool vec, F f) {
+  if (vec) f(std::true_type{});
+  else f(std::false_type{});
 }
-
-// element size of a dtype code (the logits' own alignment)
-inline uintptr_t bce_elem_mask(int dtype) { return dtype == SMOE_F32 ? 3 : 1; }
 
 }  // namespace
 
@@ -859,11 +820,11 @@ extern "C" int smoe_soft_ce_fwd(const void* logits, int dtype, const float* targ
   SMOE_REQUIRE(logits && row_loss && row_max && row_logsum && row_tsum && loss, "smoe_soft_ce_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(logits, target, nullptr, C);
-  switch (dtype) {
-    case SMOE_F32: launch_ce_fwd<float>(vec, (int)B, s, logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum); break;
-    case SMOE_F16: launch_ce_fwd<f16>(vec, (int)B, s, logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum); break;
-    default: launch_ce_fwd<bf16_bits>(vec, (int)B, s, logits, target, labels, smoothing, C, row_loss, row_max, row_logsum, row_tsum); break;
-  }
+  with_dtype(dtype, [&](auto tag) { with_vec(vec, [&](auto v) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((soft_ce_fwd_kernel<T, decltype(v)::value>), dim3((unsigned)B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels,
+                       smoothing, C, row_loss, row_max, row_logsum, row_tsum);
+  }); });
   SMOE_CHECK_LAUNCH("smoe_soft_ce_fwd");
   hipLaunchKernelGGL(row_mean_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_loss, (int)B, loss);
   SMOE_CHECK_LAUNCH("smoe_soft_ce_fwd (mean)");
@@ -879,11 +840,11 @@ extern "C" int smoe_soft_ce_bwd(const void* logits, int dtype, const float* targ
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(logits, target, dlogits, C);
   const dim3 grid((unsigned)((C + LOSS_THREADS * CE_K - 1) / (LOSS_THREADS * CE_K)), (unsigned)B);
-  switch (dtype) {
-    case SMOE_F32: launch_ce_bwd<float>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
-    case SMOE_F16: launch_ce_bwd<f16>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
-    default: launch_ce_bwd<bf16_bits>(vec, grid, s, logits, target, labels, smoothing, (int)B, C, row_max, row_logsum, row_tsum, g, dlogits); break;
-  }
+  with_dtype(dtype, [&](auto tag) { with_vec(vec, [&](auto v) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((soft_ce_bwd_kernel<T, decltype(v)::value>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, labels, smoothing,
+                       (int)B, C, row_max, row_logsum, row_tsum, g, (T*)dlogits);
+  }); });
   SMOE_CHECK_LAUNCH("smoe_soft_ce_bwd");
   return 0;
 }
@@ -903,11 +864,11 @@ extern "C" int smoe_eval_metrics(const void* logits, int dtype, const int64_t* l
   SMOE_REQUIRE(logits && labels && row_loss && row_rank && batch, "smoe_eval_metrics: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(logits, nullptr, nullptr, C);
-  switch (dtype) {
-    case SMOE_F32: launch_eval_row<float>(vec, (int)B, s, logits, labels, C, row_loss, row_rank); break;
-    case SMOE_F16: launch_eval_row<f16>(vec, (int)B, s, logits, labels, C, row_loss, row_rank); break;
-    default: launch_eval_row<bf16_bits>(vec, (int)B, s, logits, labels, C, row_loss, row_rank); break;
-  }
+  with_dtype(dtype, [&](auto tag) { with_vec(vec, [&](auto v) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((eval_row_kernel<T, decltype(v)::value>), dim3((unsigned)B), dim3(LOSS_THREADS), 0, s, (const T*)logits, labels, C, row_loss,
+                       row_rank);
+  }); });
   SMOE_CHECK_LAUNCH("smoe_eval_metrics");
   hipLaunchKernelGGL(eval_batch_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_loss, row_rank, (int)B, tk, nk, batch, acc);
   SMOE_CHECK_LAUNCH("smoe_eval_metrics (batch)");
@@ -925,9 +886,12 @@ extern "C" int smoe_distill_fwd(const void* student, int s_dtype, const void* te
   SMOE_REQUIRE(student && teacher && base_loss && row_val && row_stats && row_label && distill_loss && loss, "smoe_distill_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(student, teacher, nullptr, C);
-#define DF(TS, TT) launch_distill_fwd<TS, TT>(vec, s, student, teacher, mode, tau, (int)B, C, row_val, row_stats, row_label)
-  DISTILL_PAIRS(DF)
-#undef DF
+  with_dtype(s_dtype, [&](auto stag) { with_dtype(t_dtype, [&](auto ttag) { with_vec(vec, [&](auto v) {
+    using TS = typename decltype(stag)::T;
+    using TT = typename decltype(ttag)::T;
+    hipLaunchKernelGGL((distill_fwd_kernel<TS, TT, decltype(v)::value>), dim3((unsigned)B), dim3(LOSS_THREADS), 0, s, (const TS*)student,
+                       (const TT*)teacher, mode, tau, (int)B, C, row_val, row_stats, row_label);
+  }); }); });
   SMOE_CHECK_LAUNCH("smoe_distill_fwd");
   hipLaunchKernelGGL(distill_blend_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_val, (int)B, C, mode, tau, alpha, base_loss, distill_loss, loss);
   SMOE_CHECK_LAUNCH("smoe_distill_fwd (blend)");
@@ -946,9 +910,12 @@ extern "C" int smoe_distill_bwd(const void* student, int s_dtype, const void* te
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(student, teacher, dlogits, C);
   const dim3 grid((unsigned)((C + LOSS_THREADS * CE_K - 1) / (LOSS_THREADS * CE_K)), (unsigned)B);
-#define DB(TS, TT) launch_distill_bwd<TS, TT>(vec, grid, s, student, teacher, mode, tau, alpha, (int)B, C, row_stats, row_label, g, dlogits)
-  DISTILL_PAIRS(DB)
-#undef DB
+  with_dtype(s_dtype, [&](auto stag) { with_dtype(t_dtype, [&](auto ttag) { with_vec(vec, [&](auto v) {
+    using TS = typename decltype(stag)::T;
+    using TT = typename decltype(ttag)::T;
+    hipLaunchKernelGGL((distill_bwd_kernel<TS, TT, decltype(v)::value>), grid, dim3(LOSS_THREADS), 0, s, (const TS*)student, (const TT*)teacher,
+                       mode, tau, alpha, (int)B, C, row_stats, row_label, g, (TS*)dlogits);
+  }); }); });
   SMOE_CHECK_LAUNCH("smoe_distill_bwd");
   return 0;
 }
@@ -959,15 +926,15 @@ extern "C" int smoe_bce_fwd(const void* logits, int dtype, const float* target, 
   SMOE_REQUIRE(B >= 0 && B <= GRID_Y_MAX && C > 0 && C <= (1 << 30), "smoe_bce_fwd: bad sizes (B <= 65535, 0 < C <= 2^30)");
   if (B == 0) return 0;
   SMOE_REQUIRE(logits && target && row_loss && loss, "smoe_bce_fwd: null pointer");
-  SMOE_REQUIRE(((uintptr_t)logits & bce_elem_mask(dtype)) == 0 && (((uintptr_t)target | (uintptr_t)row_loss | (uintptr_t)loss) & 3) == 0,
+  SMOE_REQUIRE((uintptr_t)logits % smoe_dtype_size(dtype) == 0 && (((uintptr_t)target | (uintptr_t)row_loss | (uintptr_t)loss) & 3) == 0,
                "smoe_bce_fwd: misaligned pointer (logits to its element size, the f32 buffers to 4 bytes)");
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(logits, target, nullptr, C);
-  switch (dtype) {
-    case SMOE_F32: launch_bce_fwd<float>(vec, (int)B, s, logits, target, binarize, C, row_loss); break;
-    case SMOE_F16: launch_bce_fwd<f16>(vec, (int)B, s, logits, target, binarize, C, row_loss); break;
-    default: launch_bce_fwd<bf16_bits>(vec, (int)B, s, logits, target, binarize, C, row_loss); break;
-  }
+  with_dtype(dtype, [&](auto tag) { with_vec(vec, [&](auto v) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((bce_fwd_kernel<T, decltype(v)::value>), dim3((unsigned)B), dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, C,
+                       row_loss);
+  }); });
   SMOE_CHECK_LAUNCH("smoe_bce_fwd");
   hipLaunchKernelGGL(bce_mean_kernel, dim3(1), dim3(LOSS_THREADS), 0, s, row_loss, (int)B, C, loss);
   SMOE_CHECK_LAUNCH("smoe_bce_fwd (mean)");
@@ -980,16 +947,16 @@ extern "C" int smoe_bce_bwd(const void* logits, int dtype, const float* target, 
   SMOE_REQUIRE(B >= 0 && B <= GRID_Y_MAX && C > 0 && C <= (1 << 30), "smoe_bce_bwd: bad sizes (B <= 65535, 0 < C <= 2^30)");
   if (B == 0) return 0;
   SMOE_REQUIRE(logits && target && g && dlogits, "smoe_bce_bwd: null pointer");
-  SMOE_REQUIRE((((uintptr_t)logits | (uintptr_t)dlogits) & bce_elem_mask(dtype)) == 0 && (((uintptr_t)target | (uintptr_t)g) & 3) == 0,
+  SMOE_REQUIRE(((uintptr_t)logits | (uintptr_t)dlogits) % smoe_dtype_size(dtype) == 0 && (((uintptr_t)target | (uintptr_t)g) & 3) == 0,
                "smoe_bce_bwd: misaligned pointer (logits and dlogits to their element size, the f32 buffers to 4 bytes)");
   hipStream_t s = (hipStream_t)stream;
   const bool vec = ce_vec_ok(logits, target, dlogits, C);
   const dim3 grid((unsigned)((C + LOSS_THREADS * CE_K - 1) / (LOSS_THREADS * CE_K)), (unsigned)B);
-  switch (dtype) {
-    case SMOE_F32: launch_bce_bwd<float>(vec, grid, s, logits, target, binarize, (int)B, C, g, dlogits); break;
-    case SMOE_F16: launch_bce_bwd<f16>(vec, grid, s, logits, target, binarize, (int)B, C, g, dlogits); break;
-    default: launch_bce_bwd<bf16_bits>(vec, grid, s, logits, target, binarize, (int)B, C, g, dlogits); break;
-  }
+  with_dtype(dtype, [&](auto tag) { with_vec(vec, [&](auto v) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((bce_bwd_kernel<T, decltype(v)::value>), grid, dim3(LOSS_THREADS), 0, s, (const T*)logits, target, binarize, (int)B, C, g,
+                       (T*)dlogits);
+  }); });
   SMOE_CHECK_LAUNCH("smoe_bce_bwd");
   return 0;
 }

@@ -146,6 +146,34 @@ def test_binarize_rule_on_special_target_values():
     assert torch.equal(crit(x, tiny), _own(x, torch.ones_like(x), False)[0])
 
 
+# ------------------------------------------------------------------------------------------------ the two paths of the backward
+@pytest.mark.parametrize("binarize", [False, True], ids=["raw", "binarize"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+def test_bce_bwd_base_that_is_not_16_byte_aligned_takes_the_element_path_and_writes_the_same_bits(dtype, binarize):
+    """C = 2056 = one step of 256 x 8 logits + one vector; the same logits, targets and g once on 16-byte aligned bases (8 logits per
+    lane) and once with logits and dlogits 4 bytes into larger buffers (element by element)."""
+    B, C = 3, 2056
+    n = B * C
+    words = 4 // torch.empty(0, dtype=dtype).element_size()          # elements in 4 bytes
+    x = cases.logits(B, C, 4.0, dtype).to(DEV)
+    t = cases.targets("mixup", B, C).to(DEV)
+    g = _scalar(512.0)
+    assert x.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 0 and C % 8 == 0
+    dx = ops.bce_bwd(x, t, g, binarize)
+    assert dx.data_ptr() % 16 == 0
+    store = torch.zeros(n + 16, dtype=dtype, device=DEV)
+    xo = store[words:words + n].view(B, C)
+    xo.copy_(x)
+    assert xo.data_ptr() % 16 == 4 and xo.is_contiguous()
+    out = torch.zeros(n + 16, dtype=dtype, device=DEV)
+    rc = sm._lib.load().smoe_bce_bwd(xo.data_ptr(), ops.dtype_code(dtype), t.data_ptr(), int(binarize), B, C, g.data_ptr(),
+                                     out.data_ptr() + 4, ops._stream(x))
+    assert rc == 0
+    assert torch.equal(_bits(out[words:words + n].view(B, C)), _bits(dx))
+    assert bool(dx.float().abs().sum() > 0)
+    assert float(out[:words].float().abs().sum()) == 0 and float(out[words + n:].float().abs().sum()) == 0, "nothing written outside dlogits"
+
+
 # ------------------------------------------------------------------------------------------------- determinism and independence
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
 @pytest.mark.parametrize("C", [10, 1000, 1001])

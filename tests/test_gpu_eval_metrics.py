@@ -83,9 +83,11 @@ def _bars(x, labels):
 
 
 @pytest.mark.parametrize("scale", [1.0, 30.0])
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
-@pytest.mark.parametrize("B,C", [(64, 1000), (3, 1001)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("B,C", [(64, 1000), (3, 1001), (257, 2056), (2, 4099)])
 def test_loss_is_soft_ce_fwds_bits_and_within_torchs_own_error(B, C, dtype, scale):
+    """(257, 2056): more rows than the mean kernels' 256 threads and more than one 2048-logit step on the 8-per-lane path; (2, 4099):
+    more than one step on the element path."""
     g = torch.Generator(device=DEV).manual_seed(B + C)
     x = (torch.randn(B, C, generator=g, device=DEV) * scale).to(dtype)
     labels = torch.randint(0, C, (B,), generator=g, device=DEV)

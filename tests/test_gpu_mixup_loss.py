@@ -409,6 +409,37 @@ def test_mixup_images_on_a_base_that_is_not_16_byte_aligned_takes_the_element_pa
     assert torch.equal(got, want) and torch.equal(t, want_t) and m.lam != 1.
 
 
+@pytest.mark.parametrize("form", ["dense", "labels"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+def test_soft_ce_bwd_base_that_is_not_16_byte_aligned_takes_the_element_path_and_writes_the_same_bits(dtype, form):
+    """C = 2056 = one step of 256 x 8 logits + one vector; the same logits, row statistics and g once on 16-byte aligned bases (8
+    logits per lane) and once with logits and dlogits 4 bytes into larger buffers (element by element)."""
+    B, C, smoothing = 3, 2056, 0.1
+    n = B * C
+    words = 4 // torch.empty(0, dtype=dtype).element_size()          # elements in 4 bytes
+    x = (torch.randn(B, C, generator=_gen(71), device=DEV) * 3).to(dtype)
+    t, labels = _dense_targets(B, C, 72)
+    t, labels = (t.contiguous(), None) if form == "dense" else (None, labels)
+    g = torch.tensor(3.0, dtype=torch.float32, device=DEV)
+    _, rows = ops.soft_ce_fwd(x, t, labels, smoothing)
+    assert x.data_ptr() % 16 == 0 and (t is None or t.data_ptr() % 16 == 0) and C % 8 == 0
+    dx = ops.soft_ce_bwd(x, rows, g, t, labels, smoothing)
+    assert dx.data_ptr() % 16 == 0
+    store = torch.zeros(n + 16, dtype=dtype, device=DEV)
+    xo = store[words:words + n].view(B, C)
+    xo.copy_(x)
+    assert xo.data_ptr() % 16 == 4 and xo.is_contiguous()
+    out = torch.zeros(n + 16, dtype=dtype, device=DEV)
+    rc = sm._lib.load().smoe_soft_ce_bwd(xo.data_ptr(), ops.dtype_code(dtype), ops._ptr(t), ops._ptr(labels), smoothing, B, C,
+                                         rows.data_ptr() + 4 * B, rows.data_ptr() + 8 * B, rows.data_ptr() + 12 * B, g.data_ptr(),
+                                         out.data_ptr() + 4, ops._stream(x))
+    assert rc == 0
+    bits = torch.int32 if dtype == torch.float32 else torch.int16
+    assert torch.equal(out[words:words + n].view(B, C).view(bits), dx.view(bits))
+    assert bool(dx.float().abs().sum() > 0)
+    assert float(out[:words].float().abs().sum()) == 0 and float(out[words + n:].float().abs().sum()) == 0, "nothing written outside dlogits"
+
+
 def test_batch_mode_calls_cover_mixup_cutmix_and_untouched():
     m = sm.Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, prob=0.7, mode="batch", label_smoothing=0.1, num_classes=1000)
     np.random.seed(0)
