@@ -540,6 +540,34 @@ int smoe_step_advance(float* step, const float* found_inf, void* stream);
  * skip (may be NULL): a device f32 flag; non-zero = the launch writes nothing.  No allocation, no synchronisation.          */
 int smoe_ema_update_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, float decay,
                           float one_minus_decay, const float* skip, void* stream);
+/* LAMB (timm.optim.Lamb 0.4.12 / 0.5; the DeiT-III recipes' --opt lamb, main.py:90-96, 729-731) on the tables of
+ * smoe_adamw_step_multi: tab, blk and shadow as there; hyp = f32 [3][n_tensors]: lr, weight_decay and the adapt flag
+ * (weight_decay != 0 or always_adapt; 0 = the tensor's trust ratio is 1).  Four launches per step, every one of which returns at
+ * once when *found_inf != 0 (found_inf may be NULL), none of which allocates or synchronises; every sum has a fixed order.
+ * smoe_lamb_clip         : ONE workgroup.  partial = the block partials of smoe_grad_sumsq_multi over every gradient of the step
+ *                          (n_partials of them, summed in double): out[1] = G = sqrt(sum) * *mult_num / *mult_den (NULL = 1: the
+ *                          partials were taken with *mult_den, the optimizer reads its gradients times *mult_num), out[0] = clip =
+ *                          G > max_grad_norm ? G / max_grad_norm : 1; max_grad_norm <= 0 = no clipping (timm's None).
+ * smoe_lamb_stage1_multi : g' = g * *grad_mult / *clip (NULL = 1 each); exp_avg = exp_avg * beta1 + beta3 * g'; exp_avg_sq =
+ *                          exp_avg_sq * beta2 + (1 - beta2) * g'^2, in place; u = (exp_avg / bc1) / (sqrt(exp_avg_sq) / sqrt(bc2) +
+ *                          eps) + weight_decay * p with bc1 = 1 - beta1^t, bc2 = 1 - beta2^t (t = *step, already advanced; both 1
+ *                          when bias_correction == 0).  u is NOT stored: norms = f32 [2][n_blocks] receives per block sum(p^2) and
+ *                          sum(u^2), for tensors with the adapt flag on.
+ * smoe_lamb_trust_multi  : one wave per tensor.  first = int32 [n_tensors + 1]: the first block of every tensor (first[n_tensors] =
+ *                          n_blocks).  trust[t] = ||p|| / ||u|| from the block partials, in double, 1 where either norm is 0 or the
+ *                          adapt flag is off; trust_clip != 0: at most 1.
+ * smoe_lamb_stage2_multi : u again, by the same device function from the same operands (the new moments, the old p), then
+ *                          p -= lr * (trust[t] * u); where shadow holds an image of p, the updated value is written there too.  */
+int smoe_lamb_clip(const float* partial, int64_t n_partials, const float* mult_num, const float* mult_den, float max_grad_norm,
+                   const float* found_inf, float* out, void* stream);
+int smoe_lamb_stage1_multi(const int64_t* tab, const float* hyp, int n_tensors, const int32_t* blk, int64_t n_blocks, int g_dtype,
+                           double beta1, double beta2, float beta3, float eps, int bias_correction, const float* step,
+                           const float* grad_mult, const float* clip, const float* found_inf, float* norms, void* stream);
+int smoe_lamb_trust_multi(const float* norms, int64_t n_blocks, const int32_t* first, const float* hyp, int n_tensors,
+                          int trust_clip, const float* found_inf, float* trust, void* stream);
+int smoe_lamb_stage2_multi(const int64_t* tab, const float* hyp, int n_tensors, const int32_t* blk, int64_t n_blocks, double beta1,
+                           double beta2, float eps, int bias_correction, const float* step, const float* trust,
+                           const float* found_inf, const int64_t* shadow, void* stream);
 
 /* ---- the recipe around the model (engine.py:46-47, 54; main.py:505-517 timm.data.Mixup, main.py:653-661 timm.loss.
  * SoftTargetCrossEntropy / LabelSmoothingCrossEntropy; the reference's default run is --mixup 0.8 --cutmix 1.0 --smoothing 0.1).

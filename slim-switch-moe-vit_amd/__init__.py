@@ -8,7 +8,7 @@ from .vit import (Block, VisionTransformer, DistilledVisionTransformer, create_m
                   deit_small_distilled_patch16_224, deit_base_distilled_patch16_224, deit_base_distilled_patch16_384)
 from .resmoe import *  # noqa: F401,F403
 from .engine import evaluate, accuracy, EvalMeter, train_one_epoch, GraphedForward, GraphedTrainStep  # noqa: F401
-from .optim import AdamW, ModelEma, NativeScaler, invalidate_weight_images  # noqa: F401
+from .optim import AdamW, Lamb, ModelEma, NativeScaler, invalidate_weight_images  # noqa: F401
 from .mixup import Mixup  # noqa: F401
 from .loss import SoftTargetCrossEntropy, LabelSmoothingCrossEntropy, DistillationLoss, BCEWithLogitsLoss  # noqa: F401
 

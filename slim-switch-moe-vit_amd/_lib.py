@@ -107,6 +107,13 @@ SIGNATURES = {
     "smoe_amp_update": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_int, c_void_p]),
     "smoe_step_advance": (c_int, [c_void_p, c_void_p, c_void_p]),
     "smoe_ema_update_multi": (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
+    "smoe_lamb_clip": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "smoe_lamb_stage1_multi": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "smoe_lamb_trust_multi": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "smoe_lamb_stage2_multi": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "smoe_mixup_images": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "smoe_mixup_target": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p]),
     "smoe_soft_ce_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p,
@@ -152,7 +159,7 @@ _lib = None
 
 # what csrc/Makefile hashes into smoe_build_id(): the same names, sorted as strings, relative to csrc/
 _HASHED = ["api.hip", "router.hip", "router16.hip", "gate.hip", "dispatch.hip", "gemm.hip", "backward.hip", "attention.hip",
-           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "smoe_common.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
+           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "lamb.hip", "smoe_common.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
            "../../include/slimmoe.h", "Makefile"]
 
 

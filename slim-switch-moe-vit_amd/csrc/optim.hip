@@ -9,6 +9,7 @@
 //                       the step count lives on the device (no host sync anywhere in the step)
 //   smoe_amp_update   : GradScaler.update() (growth / backoff of the loss scale) + the optimizer's step counter
 //   smoe_ema_update_multi : the weight EMA after the step (timm ModelEma.update), every tensor in one launch, skippable from the device
+// LAMB (timm.optim.Lamb: --opt lamb) reads the same tables -- and the block partials of smoe_grad_sumsq_multi -- from lamb.hip.
 #include "smoe_common.h"
 #include <type_traits>
 

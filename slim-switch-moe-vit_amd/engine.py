@@ -402,8 +402,9 @@ class GraphedTrainStep:
                 and not getattr(optimizer, "is_second_order", False))
 
     def _hyper(self):
+        baked = getattr(self.optimizer, "_slimmoe_baked_hyper", None)   # further values an optimizer's captured launches hold
         return (tuple((g.get("lr"), g.get("weight_decay"), tuple(g.get("betas", ())), g.get("eps")) for g in self.optimizer.param_groups),
-                None if self.model_ema is None else self.model_ema.decay)
+                None if self.model_ema is None else self.model_ema.decay, None if baked is None else baked())
 
     def eager(self, samples, targets):
         """The step itself (also what gets captured).  Returns the detached f32 loss."""

@@ -16,6 +16,11 @@ scale, the non-finite flag, the clip coefficient and the step count all living o
 ``AdamW`` and ``NativeScaler`` keep the call signatures, ``state_dict`` keys and numerics of what they replace; CPU
 tensors (and non-f32 parameters) fall back to the torch composition, which is also what the tests compare against.
 
+``Lamb`` is ``timm.optim.Lamb`` (the DeiT-III recipes' ``--opt lamb``; the reference hands ``--opt`` to timm's factory) restated, with a
+fused step of four launches (csrc/lamb.hip) that keeps the global gradient norm, the trust ratios and the step count on the device; its
+global norm comes out of ``NativeScaler``'s own pass over the gradients (``wants_grad_sumsq``), so the step is the same two passes over
+the gradients as AdamW's plus one more over the parameters and moments.
+
 ``ModelEma`` is ``timm.utils.ModelEma`` (the reference trains with ``--model-ema`` on: main.py:81-84, 599-606; engine.py:77-78) with
 its per-step update -- four torch launches per state-dict entry upstream -- as ONE launch of ``smoe_ema_update_multi``, bit-equal to
 timm's line and skippable from the device, so that the graphed training step can capture it.
@@ -236,6 +241,283 @@ def _bump_versions(tensors) -> None:
         invalidate_all()
 
 
+_first_cache = {}     # (device, numels) -> int32 [n_t + 1] on the device: first block of every tensor in _block_table's order
+
+
+def _first_block_table(numels, device):
+    """First 16K-element block of every tensor (and the block count at the end): what smoe_lamb_trust_multi walks a tensor's block
+    partials by.  Depends on the tensor sizes only, cached next to ``_block_table``."""
+    key = (str(device), tuple(numels))
+    hit = _first_cache.get(key)
+    if hit is None:
+        first = [0]
+        for n in numels:
+            first.append(first[-1] + (n + SUMSQ_BLOCK - 1) // SUMSQ_BLOCK)
+        if len(_first_cache) > 16:
+            _first_cache.clear()
+        hit = _first_cache[key] = torch.tensor(first, dtype=torch.int32).to(device)
+    return hit
+
+
+def _grad_sumsq_partials(grads, mul, found_inf, device):
+    """One ``smoe_grad_sumsq_multi`` launch per gradient dtype over ``grads`` (non-empty device tensors): the list of block-partial
+    tensors of sum((g * *mul)^2), ``mul`` / ``found_inf`` optional device f32[1]."""
+    lib = _lib.load()
+    by_dtype = {}
+    for g in grads:
+        by_dtype.setdefault(g.dtype, []).append(g)
+    partials = []
+    for gdt, gs in by_dtype.items():
+        blk, nb = _block_table([g.numel() for g in gs], device)
+        zeros = [0] * len(gs)
+        tab = _pointer_table([zeros, [g.data_ptr() for g in gs], zeros, zeros, [g.numel() for g in gs]], device)
+        part = torch.empty(sum(nb), dtype=torch.float32, device=device)
+        rc = lib.smoe_grad_sumsq_multi(tab.data_ptr(), len(gs), blk.data_ptr(), sum(nb), ops.dtype_code(gdt), ops._ptr(mul),
+                                       part.data_ptr(), ops._ptr(found_inf), ops._stream(part))
+        _lib.check(rc, "smoe_grad_sumsq_multi")
+        partials.append(part)
+    return partials
+
+
+class Lamb(torch.optim.Optimizer):
+    """``timm.optim.Lamb`` (timm 0.4.12 / 0.5: the DeiT-III recipes' ``--opt lamb``; main.py:90-96, 729-731) with a fused HIP step.
+
+        G    = sqrt(sum over every p with a gradient, all groups, of sum(grad^2));   clip = G / max_grad_norm if G > max_grad_norm else 1
+        per group: step += 1; beta3 = 1 - beta1 if grad_averaging else 1; bc1, bc2 = 1 - beta1^step, 1 - beta2^step (1 without bias_correction)
+        per p:     g = grad / clip;  exp_avg = exp_avg * beta1 + beta3 * g;  exp_avg_sq = exp_avg_sq * beta2 + (1 - beta2) * g * g
+                   u = (exp_avg / bc1) / (sqrt(exp_avg_sq) / sqrt(bc2) + eps) + weight_decay * p
+                   if weight_decay != 0 or always_adapt:  r = ||p|| / ||u|| (1 where either is 0; at most 1 with trust_clip);  u *= r
+                   p -= lr * u
+
+    State per parameter: ``exp_avg``, ``exp_avg_sq``; the step count is ``param_groups[i]['step']`` (timm's layout, which checkpoints
+    keep).  ``max_grad_norm`` is read from the defaults, as timm does.
+
+    f32 contiguous parameters on one GPU with contiguous f32 / f16 / bf16 gradients take four launches per (gradient dtype, betas, eps)
+    batch -- ``smoe_lamb_clip``, ``smoe_lamb_stage1_multi``, ``smoe_lamb_trust_multi``, ``smoe_lamb_stage2_multi`` (csrc/lamb.hip) --
+    with G, the clip factor, the trust ratios and the step count on the device: no host sync, so the step can be captured.  The 16-bit
+    operand images of the weights are written by the last launch.  If ANY tensor of the step is not of that kind (CPU tensors, non-f32
+    parameters, non-contiguous gradients, several devices) the whole step is the rule above in f32 torch ops.
+
+    ``step(grad_mult=None, found_inf=None, grad_sumsq=None)``: device f32[1] scalars as for ``AdamW`` -- every gradient counts times
+    ``grad_mult``, a non-zero ``found_inf`` skips the step and its count.  ``grad_sumsq = (partials, taken_with)``: block partials of
+    ``smoe_grad_sumsq_multi`` over every gradient of this optimizer, taken with the multiplier ``taken_with`` -- ``NativeScaler`` hands
+    over the ones of its own non-finite / clipping pass (``wants_grad_sumsq``), so that G costs no second pass over the gradients; G is
+    then ``grad_mult / taken_with`` times the root of their sum, the norm of the gradients a stock optimizer would see after unscale
+    and clip.  Called bare, the step makes the norm pass itself.  ``last_grad_norm`` (f32[2] on the device: clip, G) and
+    ``trust_ratios()`` expose what the last applied step used.
+
+    The global norm is over THIS process's gradients, as timm's is: expert-parallel models (rank-private experts) get a rank-local
+    norm, which is not what a single-process run of the same model computes."""
+
+    supports_device_scalars = True
+    _slimmoe_refreshes_images = True     # (_foreign_step_hook: this step bumps the versions / refreshes the 16-bit images itself)
+    wants_grad_sumsq = True              # NativeScaler: pass the norm pass's block partials to step()
+
+    def __init__(self, params, lr: float = 1e-3, bias_correction: bool = True, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.01, grad_averaging: bool = True, max_grad_norm: Optional[float] = 1.0,
+                 trust_clip: bool = False, always_adapt: bool = False):
+        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
+            raise ValueError("Lamb: invalid hyper-parameter")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("Lamb: max_grad_norm must be positive (or None: no clipping)")
+        super().__init__(params, dict(lr=lr, bias_correction=bias_correction, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      grad_averaging=grad_averaging, max_grad_norm=max_grad_norm, trust_clip=trust_clip,
+                                      always_adapt=always_adapt))
+        self._step_dev = {}       # device -> f32[1] number of updates applied so far (advanced on the device)
+        self._norm_dev = {}       # device -> f32[2]: clip, G of the last applied step
+        self._trust = []          # [(parameters, f32 [n] trust ratios on the device or a list of floats)] of the last step
+        self.last_grad_norm = None
+
+    def _slimmoe_baked_hyper(self):
+        """What a captured step bakes in besides lr / weight decay / betas / eps (engine.GraphedTrainStep._hyper)."""
+        return (self.defaults["max_grad_norm"],) + tuple(
+            (g["bias_correction"], g["grad_averaging"], g["trust_clip"], g["always_adapt"]) for g in self.param_groups)
+
+    def _group_steps(self) -> int:
+        return max([int(g.get("step", 0)) for g in self.param_groups] or [0])
+
+    def _step_counter(self, device) -> torch.Tensor:
+        t = self._step_dev.get(device)
+        if t is None:        # (created from the groups' count: a loaded checkpoint, or earlier steps on the torch composition)
+            t = self._step_dev[device] = torch.full((1,), float(self._group_steps()), dtype=torch.float32, device=device)
+        return t
+
+    def _steps_to_groups(self) -> None:
+        """param_groups[i]['step'] = the device-side count (steps skipped for non-finite gradients are not counted)."""
+        for t in self._step_dev.values():
+            n = int(float(t))
+            for group in self.param_groups:
+                if n or "step" in group:
+                    group["step"] = n
+
+    def state_dict(self):
+        """timm's layout: ``state[i] = {exp_avg, exp_avg_sq}``, ``param_groups[i]['step']``.  On the HIP path the count is read back
+        from the device here -- a checkpoint is the one place where the host may ask."""
+        self._steps_to_groups()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """Restores the moments and the step count the bias correction uses (from ``param_groups[i]['step']``)."""
+        super().load_state_dict(state_dict)
+        self._step_dev = {}       # (re-created from the loaded groups at the next fused step)
+
+    def trust_ratios(self):
+        """{parameter: trust ratio the last applied step multiplied its update by} (asks the host)."""
+        out = {}
+        for params, r in self._trust:
+            vals = r.tolist() if isinstance(r, torch.Tensor) else r
+            out.update(zip(params, vals))
+        return out
+
+    @staticmethod
+    def _fusable(p, g, m, v) -> bool:
+        return (_hip_ok(p) and g.is_cuda and g.device == p.device and g.is_contiguous() and g.dtype in ops._DT
+                and m.dtype == torch.float32 and v.dtype == torch.float32 and m.is_contiguous() and v.is_contiguous()
+                and m.device == p.device and v.device == p.device
+                and p.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0
+                and g.data_ptr() % (4 * g.element_size()) == 0)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_mult: Optional[torch.Tensor] = None, found_inf: Optional[torch.Tensor] = None,
+             grad_sumsq=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        entries = []      # (group, p, g, exp_avg, exp_avg_sq) of every non-empty parameter with a gradient
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("Lamb does not support sparse gradients, consider SparseAdam instead.")
+                st = self.state[p]
+                if not st:
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if p.numel():
+                    entries.append((group, p, p.grad, st["exp_avg"], st["exp_avg_sq"]))
+        if not entries:
+            return loss
+        dev = entries[0][1].device
+        if all(p.device == dev and self._fusable(p, g, m, v) for _, p, g, m, v in entries):
+            self._fused_step(entries, dev, grad_mult, found_inf, grad_sumsq)
+        else:
+            self._torch_step(entries, grad_mult, found_inf)
+        return loss
+
+    def _torch_step(self, entries, grad_mult, found_inf) -> None:
+        """The rule in f32 torch ops (CPU tensors, other dtypes, non-contiguous gradients)."""
+        import math
+        if self._step_dev:                  # earlier steps ran fused: carry their count over
+            self._steps_to_groups()
+            self._step_dev = {}
+        if found_inf is not None and float(found_inf) != 0.0:
+            return
+        gm = float(grad_mult) if grad_mult is not None else 1.0
+        grads = [g.float() * gm for _, _, g, _, _ in entries]
+        G = math.sqrt(sum(float(gg.pow(2).sum()) for gg in grads))
+        mgn = self.defaults["max_grad_norm"]
+        clip = G / mgn if (mgn is not None and G > mgn) else 1.0
+        self.last_grad_norm = torch.tensor([clip, G], dtype=torch.float32)
+        stepped, params, ratios = set(), [], []
+        for (group, p, _, m, v), gg in zip(entries, grads):
+            if id(group) not in stepped:
+                group["step"] = int(group.get("step", 0)) + 1
+                stepped.add(id(group))
+            b1, b2 = group["betas"]
+            beta3 = 1 - b1 if group["grad_averaging"] else 1.0
+            t = group["step"]
+            bc1, bc2 = (1 - b1 ** t, 1 - b2 ** t) if group["bias_correction"] else (1.0, 1.0)
+            lr, wd = group["lr"], group["weight_decay"]
+            p32, m32, v32 = p.float(), m.float(), v.float()      # (of an f32 tensor: the tensor itself, updated in place)
+            gg = gg / clip
+            m32.mul_(b1).add_(gg, alpha=beta3)
+            v32.mul_(b2).addcmul_(gg, gg, value=1 - b2)
+            u = (m32 / bc1).div_((v32.sqrt() / math.sqrt(bc2)).add_(group["eps"]))
+            if wd != 0:
+                u.add_(p32, alpha=wd)
+            r = 1.0
+            if wd != 0 or group["always_adapt"]:
+                w_norm, u_norm = float(p32.norm(2.0)), float(u.norm(2.0))
+                if w_norm > 0 and u_norm > 0:
+                    r = w_norm / u_norm
+                if group["trust_clip"]:
+                    r = min(r, 1.0)
+                u.mul_(r)
+            p32.add_(u, alpha=-lr)
+            if m32 is not m:
+                m.copy_(m32)
+            if v32 is not v:
+                v.copy_(v32)
+            if p32 is not p:
+                p.copy_(p32)
+            params.append(p)
+            ratios.append(r)
+        self._trust = [(params, ratios)]
+
+    def _fused_step(self, entries, dev, grad_mult, found_inf, grad_sumsq) -> None:
+        lib = _lib.load()
+        stream = ops._stream(entries[0][1])
+        step_t = self._step_counter(dev)
+        # G and the clip factor, from the norm pass's block partials (the scaler's, or a pass of this step's own)
+        if grad_sumsq is not None:
+            partials, num, den = list(grad_sumsq[0]), grad_mult, grad_sumsq[1]
+        else:
+            partials, num, den = _grad_sumsq_partials([g for _, _, g, _, _ in entries], grad_mult, None, dev), None, None
+        part = partials[0] if len(partials) == 1 else torch.cat(partials)
+        out = self._norm_dev.get(dev)
+        if out is None:
+            out = self._norm_dev[dev] = torch.tensor([1.0, 0.0], dtype=torch.float32, device=dev)
+        mgn = self.defaults["max_grad_norm"]
+        rc = lib.smoe_lamb_clip(part.data_ptr(), part.numel(), ops._ptr(num), ops._ptr(den), float(mgn) if mgn is not None else 0.0,
+                                ops._ptr(found_inf), out.data_ptr(), stream)
+        _lib.check(rc, "smoe_lamb_clip")
+        self.last_grad_norm = out
+        _lib.check(lib.smoe_step_advance(step_t.data_ptr(), ops._ptr(found_inf), stream), "smoe_step_advance")
+        batches = {}      # (grad dtype, betas, eps, bias_correction, grad_averaging, trust_clip) -> entries: four launches each
+        for ent in entries:
+            group, g = ent[0], ent[2]
+            b1, b2 = group["betas"]
+            batches.setdefault((g.dtype, float(b1), float(b2), float(group["eps"]), bool(group["bias_correction"]),
+                                bool(group["grad_averaging"]), bool(group["trust_clip"])), []).append(ent)
+        refreshed = []
+        self._trust = []
+        for (gdt, b1, b2, eps, bias, averaging, trust_clip), items in batches.items():
+            numels = [p.numel() for _, p, _, _, _ in items]
+            blk, nb = _block_table(numels, dev)
+            first = _first_block_table(numels, dev)
+            n_blocks = sum(nb)
+            tab = _pointer_table([[p.data_ptr() for _, p, _, _, _ in items], [g.data_ptr() for _, _, g, _, _ in items],
+                                  [m.data_ptr() for _, _, _, m, _ in items], [v.data_ptr() for _, _, _, _, v in items], numels], dev)
+            hyp = _host_table([[float(gr["lr"]) for gr, _, _, _, _ in items], [float(gr["weight_decay"]) for gr, _, _, _, _ in items],
+                               [1.0 if (gr["weight_decay"] != 0 or gr["always_adapt"]) else 0.0 for gr, _, _, _, _ in items]],
+                              torch.float32, dev)
+            shadows = [shadow_of(p) if SHADOW_STEP else None for _, p, _, _, _ in items]
+            sh_tab = None
+            if any(sh is not None for sh in shadows):
+                sh_tab = _pointer_table([[sh[2].data_ptr() if sh is not None else 0 for sh in shadows],
+                                         [ops.dtype_code(sh[2].dtype) if sh is not None else 0 for sh in shadows]], dev)
+            norms = torch.empty((2, n_blocks), dtype=torch.float32, device=dev)
+            trust = torch.ones(len(items), dtype=torch.float32, device=dev)
+            rc = lib.smoe_lamb_stage1_multi(tab.data_ptr(), hyp.data_ptr(), len(items), blk.data_ptr(), n_blocks, ops.dtype_code(gdt),
+                                            b1, b2, (1.0 - b1) if averaging else 1.0, eps, int(bias), step_t.data_ptr(),
+                                            ops._ptr(grad_mult), out.data_ptr(), ops._ptr(found_inf), norms.data_ptr(), stream)
+            _lib.check(rc, "smoe_lamb_stage1_multi")
+            rc = lib.smoe_lamb_trust_multi(norms.data_ptr(), n_blocks, first.data_ptr(), hyp.data_ptr(), len(items), int(trust_clip),
+                                           ops._ptr(found_inf), trust.data_ptr(), stream)
+            _lib.check(rc, "smoe_lamb_trust_multi")
+            rc = lib.smoe_lamb_stage2_multi(tab.data_ptr(), hyp.data_ptr(), len(items), blk.data_ptr(), n_blocks, b1, b2, eps, int(bias),
+                                            step_t.data_ptr(), trust.data_ptr(), ops._ptr(found_inf), ops._ptr(sh_tab), stream)
+            _lib.check(rc, "smoe_lamb_stage2_multi")
+            self._trust.append(([p for _, p, _, _, _ in items], trust))
+            refreshed.extend((it[1], sh) for it, sh in zip(items, shadows) if sh is not None)
+        # the kernels wrote through raw pointers: move the version counters (AdamW.step), then stamp the images written above
+        _bump_versions([p for _, p, _, _, _ in entries])
+        for p, (cache, key, img) in refreshed:
+            cache.refresh(key, img, param_version(p))
+
+
 def _foreign_step_hook(optimizer, args, kwargs) -> None:
     """Global optimizer step post-hook (registered on import, below).  The modules keep 16-bit operand images of their f32
     weights, keyed on ``(param._version, data_ptr, dtype)`` (_cache.param_version).  An optimizer that updates through
@@ -273,8 +555,9 @@ class NativeScaler:
     clipping to ``clip_grad`` when it is not None (``parameters`` then required, as in timm), optimizer step skipped on
     non-finite gradients, scale update (growth 2.0 every 2000 clean steps, backoff 0.5) -- ``torch.cuda.amp.GradScaler``
     defaults.  With an optimizer that takes device scalars (``optim.AdamW``) nothing in the step syncs with the host and
-    the gradients stay SCALED in ``.grad`` (``grad_multiplier`` holds ``inv_scale x clip coefficient``); any other optimizer
-    gets the stock sequence (unscale in place, ``clip_grad_norm_``, host-checked step).
+    the gradients stay SCALED in ``.grad`` (``grad_multiplier`` holds ``inv_scale x clip coefficient``); one that sets ``wants_grad_sumsq``
+    (``optim.Lamb``) is also handed the block partials of this step's pass over the gradients: ``step(..., grad_sumsq=(partials, inv_scale))``;
+    any other optimizer gets the stock sequence (unscale in place, ``clip_grad_norm_``, host-checked step).
     ``state_dict()`` has GradScaler's keys (main.py:903 saves it, 723 loads it)."""
 
     state_dict_key = "amp_scaler"
@@ -374,7 +657,11 @@ class NativeScaler:
             coef = (float(clip_grad) / (total + 1e-6)).clamp(max=1.0)      # torch.nn.utils.clip_grad_norm_
             mult = inv_scale * coef
         self.grad_multiplier = mult.reshape(1).contiguous()
-        optimizer.step(grad_mult=self.grad_multiplier, found_inf=found_inf)
+        if getattr(optimizer, "wants_grad_sumsq", False):
+            # (optim.Lamb: its global gradient norm comes out of THIS pass's partials, taken with inv_scale -- no second pass)
+            optimizer.step(grad_mult=self.grad_multiplier, found_inf=found_inf, grad_sumsq=(partials, inv_scale))
+        else:
+            optimizer.step(grad_mult=self.grad_multiplier, found_inf=found_inf)
         rc = lib.smoe_amp_update(self._scale.data_ptr(), self._growth_tracker.data_ptr(), found_inf.data_ptr(),
                                  float(self.growth_factor), float(self.backoff_factor), int(self.growth_interval),
                                  ops._stream(self._scale))
