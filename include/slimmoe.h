@@ -134,6 +134,9 @@ int smoe_zero_row_output(const float* bg, int E, int k, const float* w2, const f
  *     dz[t]  = -<g_f[t], xn[t]> p (1 - p),  p = sigmoid(<xn[t], gate_w> + gate_b)          (d loss / d gate logit; f32 [T] or NULL)
  *     dxn[t] = g_f[t] * keep[t] + g_out[t] + dz[t] * gate_w                                 (f32 [T,d]: into the LayerNorm backward)
  * gate_on = 0 (Gate.disable: constant masks, no gradient): dxn = g_f + g_out, dz = 0.  d in {192, 384, 768, 1024}.
+ * gate_on = 2 (the SOFT gate, Gate(is_hard=False) in training, resMoE.py:72-74: m1 = p, m0 = 1 - p; mask = smoe_soft_gate_ln_fwd's
+ * (1 - p, p)):  dz[t] = +<g_f[t], xn[t]> p (1 - p)  (the opposite sign),  dxn[t] = g_f[t] * p[t] + g_out[t] + dz[t] * gate_w  (the same line,
+ * keep = mask[t, 1] = p).  Every other value of gate_on is refused.
  * The gate's parameter gradients follow from dz: dW = dz^T xn (smoe_gate_wgrad with E = 1), db = sum dz.                      */
 int smoe_skip_gate_bwd(const float* xn, const void* g_f, int g_f_dtype, const float* g_out, const float* gate_w,
                        const float* gate_b, const float* mask, int gate_on, int64_t T, int d, float* dxn, float* dz, void* stream);
@@ -141,11 +144,27 @@ int smoe_skip_gate_bwd(const float* xn, const void* g_f, int g_f_dtype, const fl
  * half's INPUT x [T,d] f32 (the normed activations, p and the gate logit are recomputed from x in registers; nothing but x and the
  * forward's decisions is read):  dx [T,d] f32 = LayerNorm backward of dxn;  out f32 [3 d + 4] = dgamma [d] | dbeta [d] | dgate_w [d] |
  * dgate_b, 0, 0, 0;  dz f32 [T] or NULL.  gamma / beta f32 [d] (NULL = 1 / 0); the other operands as in smoe_skip_gate_bwd; d % 4 == 0,
- * d <= 1024.  Deterministic (per-workgroup partial rows, two-stage ordered reduction).                                              */
+ * d <= 1024.  Deterministic (per-workgroup partial rows, two-stage ordered reduction).  gate_on = 0 / 1 / 2 as smoe_skip_gate_bwd.     */
 size_t smoe_gate_ln_bwd_workspace_bytes(int64_t T, int d);
 int smoe_gate_ln_bwd(const float* x, const void* g_f, int g_f_dtype, const float* g_out, const float* gamma, const float* beta,
                      float eps, const float* gate_w, const float* gate_b, const float* mask, int gate_on, int64_t T, int d, float* dx,
                      float* dz, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* smoe_soft_gate_ln_fwd: the front end of one gated half in TRAINING with a SOFT gate (Gate(is_hard=False), models/resMoE.py:72-74:
+ * skip_tk = 1 - p, tk = p -- no decision, so no threshold and no f64 redo), ONE pass over x [T,d] f32:
+ *   xn   = (with_ln & 1) ? LN(x) * gamma + beta : x                 (two-pass statistics; gamma / beta NULL = 1 / 0)
+ *   z    = <xn, gate_w> + gate_b (NULL = 0);  e = exp(-|z|);  p = 1 / (1 + e) or e / (1 + e) by the sign of z, 1 - p the other one
+ *   xn32 [T,d] f32: xn (the residual: out = f(tk) + xn);  tk32 [T,d] f32: xn * p, ONE f32 multiply;  tk16 [T,d] f16 / bf16: the
+ *   conversion of that f32 product (smoe_gate_ln_router's xn16 conversion);  mask [T,2] f32 = (1 - p, p).  Each may be NULL.
+ *   *skip_count (int32, may be NULL) += rint(sum_t (1 - p[t])), summed in double in a fixed order by a second one-wave launch from
+ *   per-workgroup partial sums in `workspace` (8-byte aligned, smoe_soft_gate_ln_fwd_workspace_bytes(T); unused without a counter).
+ *   A row whose 1 - p is NaN counts as 0.  No atomics, no host access: capturable.  The backward is smoe_gate_ln_bwd / smoe_skip_gate_bwd
+ *   with gate_on = 2, which recompute this pass's xn and z bit for bit.
+ * d in {192, 384, 768, 1024} (smoe_soft_gate_ln_fwd_supported), 0 <= T < 2^31 (T == 0 returns at once).                          */
+int smoe_soft_gate_ln_fwd_supported(int d);
+size_t smoe_soft_gate_ln_fwd_workspace_bytes(int64_t T);
+int smoe_soft_gate_ln_fwd(const void* x, int x_dtype, int with_ln, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                          const float* gate_w, const float* gate_b, float* xn32, void* tk16, int tk16_dtype, float* tk32, float* mask,
+                          int32_t* skip_count, int64_t T, int d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* smoe_depth_scale_rows: stochastic depth's per-sample factor (timm DropPath as models/vision_transformer.py:308 uses it: x / keep * mask)
  * expanded to the sample's rows, the form the fused stores take it in (the GEMM's per-row combine scale): mask f32 [B] (0 / 1 draws)

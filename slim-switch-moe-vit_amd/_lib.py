@@ -51,6 +51,10 @@ SIGNATURES = {
     "smoe_gate_ln_bwd_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "smoe_gate_ln_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_int,
                                  c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "smoe_soft_gate_ln_fwd_supported": (c_int, [c_int]),
+    "smoe_soft_gate_ln_fwd_workspace_bytes": (c_size_t, [c_int64]),
+    "smoe_soft_gate_ln_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
     "smoe_depth_scale_rows": (c_int, [c_void_p, ctypes.c_float, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "smoe_zero_group_fold": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -158,7 +162,7 @@ OPTIONAL = {"smoe_expert_ffn_workspace_bytes", "smoe_expert_ffn"}
 _lib = None
 
 # what csrc/Makefile hashes into smoe_build_id(): the same names, sorted as strings, relative to csrc/
-_HASHED = ["api.hip", "router.hip", "router16.hip", "gate.hip", "dispatch.hip", "gemm.hip", "backward.hip", "attention.hip",
+_HASHED = ["api.hip", "router.hip", "router16.hip", "gate.hip", "soft_gate.hip", "dispatch.hip", "gemm.hip", "backward.hip", "attention.hip",
            "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "lamb.hip", "smoe_common.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
            "../../include/slimmoe.h", "Makefile"]
 

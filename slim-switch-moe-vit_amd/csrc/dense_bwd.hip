@@ -125,6 +125,7 @@ __global__ __launch_bounds__(LNB_THREADS) void layernorm_bwd_kernel(const float*
 // read the normed activations twice more.  Everything is recomputed from x in registers:
 //     xhat = (x - mean) rstd,  xn = xhat gamma + beta,  p = sigmoid(<xn, w> + b),
 //     dz = -<g_f, xn> p (1 - p),  dxn = g_f keep + g_out + dz w,              (gate_on = 0: dz = 0, dxn = g_f + g_out)
+//     gate_on = 2 (soft gate, keep = mask[t, 1] = the forward's p): dz = +<g_f, xn> p (1 - p), the dxn line unchanged
 //     dx = rstd (dxn gamma - mean(dxn gamma) - xhat mean(dxn gamma xhat)),
 //     dgamma = sum dxn xhat,  dbeta = sum dxn,  dw = sum dz xn,  db = sum dz.
 // g_f = dL/d(the operator's masked input), g_out = dL/d(the half's output, i.e. of the residual xn), keep = mask[t, 1].
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
     // p (1 - p) = e / (1 + e)^2, e = exp(-|z|): 1 - p taken from the rounded p loses about |z| log2(e) bits once the gate saturates
     // (z = 5: 1.5e-5 relative instead of 3e-7; tests/test_value_regimes_host.py)
     const float e = expf(-fabsf(z));
-    const float dz = gate_on ? -dot * (e / ((1.0f + e) * (1.0f + e))) : 0.f;
+    const float dz = gate_on ? (gate_on == 2 ? dot : -dot) * (e / ((1.0f + e) * (1.0f + e))) : 0.f;
     agb += dz;
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
@@ -453,6 +454,7 @@ extern "C" int smoe_gate_ln_bwd(const float* x, const void* g_f, int g_f_dtype, 
                                 const float* beta, float eps, const float* gate_w, const float* gate_b, const float* mask,
                                 int gate_on, int64_t T, int d, float* dx, float* dz, float* out, void* workspace,
                                 size_t workspace_bytes, void* stream) {
+  SMOE_REQUIRE(gate_on >= 0 && gate_on <= 2, "smoe_gate_ln_bwd: bad gate_on %d (0 = disabled, 1 = hard, 2 = soft)", gate_on);
   SMOE_REQUIRE(T >= 0 && d > 0 && d % 4 == 0 && d <= 1024, "smoe_gate_ln_bwd: bad sizes T=%lld d=%d (d %% 4 == 0, d <= 1024)",
                (long long)T, d);
   SMOE_REQUIRE(out && workspace && gate_w, "smoe_gate_ln_bwd: null pointer");

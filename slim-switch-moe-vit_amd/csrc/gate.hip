@@ -110,6 +110,9 @@ __global__ __launch_bounds__(256) void zero_row_output_kernel(const float* __res
 //     dxn   = g_f * keep + g_out + dz * w
 // One pass: 16 lanes per token (the router's layout), p recomputed from xn (no saved activations beyond xn and the decisions).
 // gate_on = 0 (a disabled gate passes everything and has no gradient): dxn = g_f + g_out, dz = 0.
+// gate_on = 2 (the SOFT gate, resMoE.py:72-74: m1 = p, m0 = 1 - p; forward: soft_gate.hip): dL/dp = +<g_f, xn> (the two <g_out, xn>
+// terms cancel again), so dz has the OPPOSITE sign, dz = +<g_f, xn> p (1 - p); mask[t, 1] holds the forward's p, so the dxn line is the
+// same line with keep = p.  (The sign is a negation of `dot`: modes 0 and 1 compute the bits they always did.)
 template <typename GT, int NJ>
 __global__ __launch_bounds__(R16_THREADS, 4) void skip_gate_bwd_kernel(const float* __restrict__ xn, const GT* __restrict__ g_f,
                                                                        const float* __restrict__ g_out, const float* __restrict__ w,
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(R16_THREADS, 4) void skip_gate_bwd_kernel(const flo
     // p (1 - p) = e / (1 + e)^2, e = exp(-|z|): 1 - p taken from the rounded p loses about |z| log2(e) bits once the gate saturates
     // (z = 5: 1.5e-5 relative instead of 3e-7; tests/test_value_regimes_host.py)
     const float e = expf(-fabsf(z));
-    const float dz = gate_on ? -dot * (e / ((1.0f + e) * (1.0f + e))) : 0.f;
+    const float dz = gate_on ? (gate_on == 2 ? dot : -dot) * (e / ((1.0f + e) * (1.0f + e))) : 0.f;
     const float keep = gate_on ? mask[tc * 2 + 1] : 1.f;
     if (live) {
 #pragma unroll
@@ -186,6 +189,7 @@ int launch_skip_gate_bwd(const float* xn, const void* g_f, const float* g_out, c
 extern "C" int smoe_skip_gate_bwd(const float* xn, const void* g_f, int g_f_dtype, const float* g_out, const float* gate_w,
                                   const float* gate_b, const float* mask, int gate_on, int64_t T, int d, float* dxn, float* dz,
                                   void* stream) {
+  SMOE_REQUIRE(gate_on >= 0 && gate_on <= 2, "smoe_skip_gate_bwd: bad gate_on %d (0 = disabled, 1 = hard, 2 = soft)", gate_on);
   if (T == 0) return 0;
   SMOE_REQUIRE(xn && g_f && gate_w && dxn, "smoe_skip_gate_bwd: null pointer");
   SMOE_REQUIRE(!gate_on || mask, "smoe_skip_gate_bwd: an enabled gate needs the forward's decisions (mask)");

@@ -445,11 +445,75 @@ def gate_ln_router(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch
     return {"xn16": xn16, "xn32": xn32, "idx": idx, "idx_plan": idx_plan, "score": score, "mask": mask, "tk32": tk32}
 
 
+def soft_gate_ln_supported(d: int) -> bool:
+    return bool(_lib.load().smoe_soft_gate_ln_fwd_supported(d))
+
+
+def soft_gate_ln(x: torch.Tensor, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor], ln: Optional[tuple] = None,
+                 xn16_dtype: Optional[torch.dtype] = None, want_xn32: bool = False, want_tk32: bool = False,
+                 want_mask: bool = False, skip_count: Optional[torch.Tensor] = None):
+    """[LayerNorm +] SOFT token-skip gate in one pass (smoe_soft_gate_ln_fwd): p = sigmoid(<xn, gate_w> + gate_b), tk = xn * p.
+    ``ln`` = (weight, bias, eps) or None.  Returns gate_ln_router's dict shape: xn32 (the normed rows), xn16 (the 16-bit image of
+    ``tk``, ``xn16_dtype``), tk32 (the f32 image of ``tk``), mask = (1 - p, p) (entries that were not asked for are None; idx /
+    idx_plan / score are always None: nothing is routed here).  ``skip_count`` (int32[1]) grows by rint(sum (1 - p))."""
+    _chk(x, "x", torch.float32, 2)
+    T, d = x.shape
+    dev = x.device
+    if not soft_gate_ln_supported(d):
+        raise RuntimeError(f"soft_gate_ln: unsupported d={d} (192, 384, 768, 1024)")
+    gw = gate_w.detach().reshape(-1)
+    _chk(gw, "gate_w", torch.float32, 1)
+    if gw.numel() != d:
+        raise RuntimeError(f"gate_w: expected {d} elements")
+    gb = gate_b.detach().reshape(-1) if gate_b is not None else None
+    if gb is not None:
+        _chk(gb, "gate_b", torch.float32, 1, align=4)
+    lg = lb = None
+    eps = 0.0
+    if ln is not None:
+        lg, lb, eps = ln
+        for t, nm in ((lg, "ln_weight"), (lb, "ln_bias")):
+            if t is not None:
+                _chk(t, nm, torch.float32, 1)
+                if t.numel() != d:
+                    raise RuntimeError(f"{nm}: expected {d} elements")
+    if xn16_dtype is not None and xn16_dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("soft_gate_ln: xn16_dtype must be float16 or bfloat16")
+    xn16 = torch.empty((T, d), dtype=xn16_dtype, device=dev) if xn16_dtype is not None else None
+    xn32 = torch.empty((T, d), dtype=torch.float32, device=dev) if want_xn32 else None
+    tk32 = torch.empty((T, d), dtype=torch.float32, device=dev) if want_tk32 else None
+    mask = torch.empty((T, 2), dtype=torch.float32, device=dev) if want_mask else None
+    lib = _lib.load()
+    ws, ws_bytes = None, 0
+    if skip_count is not None:
+        _chk(skip_count, "skip_count", torch.int32, align=4)
+        ws_bytes = lib.smoe_soft_gate_ln_fwd_workspace_bytes(T)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (<= 8 KB: one partial sum per workgroup)
+    nbytes = T * d * (4 + (2 if xn16 is not None else 0) + (4 if xn32 is not None else 0) + (4 if tk32 is not None else 0))
+    with _timed("soft_gate_ln", {"bytes": nbytes}, x):
+        rc = lib.smoe_soft_gate_ln_fwd(_ptr(x), F32, GATE_WITH_LN if ln is not None else 0, _ptr(lg), _ptr(lb), float(eps), _ptr(gw),
+                                       _ptr(gb), _ptr(xn32), _ptr(xn16), dtype_code(xn16_dtype) if xn16_dtype is not None else F16,
+                                       _ptr(tk32), _ptr(mask), _ptr(skip_count), T, d, _ptr(ws), ws_bytes, _stream(x))
+    _lib.check(rc, "smoe_soft_gate_ln_fwd")
+    return {"xn16": xn16, "xn32": xn32, "idx": None, "idx_plan": None, "score": None, "mask": mask, "tk32": tk32}
+
+
+def _gate_mode(gate_on) -> int:
+    """gate_on of the two gate backward entry points: False / 0 = disabled, True / 1 = hard (straight-through), 2 = soft."""
+    if isinstance(gate_on, bool):
+        return 1 if gate_on else 0
+    if isinstance(gate_on, int) and gate_on in (0, 1, 2):
+        return gate_on
+    raise ValueError(f"gate_on: expected False / True or 0 (disabled), 1 (hard), 2 (soft), got {gate_on!r}")
+
+
 def gate_ln_bwd(x: torch.Tensor, g_f: torch.Tensor, g_out: Optional[torch.Tensor], ln_w: Optional[torch.Tensor],
                 ln_b: Optional[torch.Tensor], eps: float, gate_w: torch.Tensor, gate_b: Optional[torch.Tensor],
-                mask: Optional[torch.Tensor], gate_on: bool = True, want_dz: bool = False):
+                mask: Optional[torch.Tensor], gate_on=True, want_dz: bool = False):
     """Backward of one gated half's front end (LayerNorm -> token-skip gate) in one pass over its input x (smoe_gate_ln_bwd):
-    (dx f32 [T,d], dln_w [d], dln_b [d], dgate_w [d], dgate_b [1], dz [T] | None)."""
+    (dx f32 [T,d], dln_w [d], dln_b [d], dgate_w [d], dgate_b [1], dz [T] | None).  ``gate_on``: False / True as before, or 2 = the
+    soft gate (``mask`` = soft_gate_ln's (1 - p, p); dz takes the positive sign)."""
+    gate_on = _gate_mode(gate_on)
     _chk(x, "x", torch.float32, 2)
     _chk(g_f, "g_f", ndim=2)
     T, d = x.shape
@@ -474,15 +538,17 @@ def gate_ln_bwd(x: torch.Tensor, g_f: torch.Tensor, g_out: Optional[torch.Tensor
     ws_bytes = lib.smoe_gate_ln_bwd_workspace_bytes(T, d)
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
     rc = lib.smoe_gate_ln_bwd(_ptr(x), _ptr(g_f), dtype_code(g_f.dtype), _ptr(g_out), _ptr(ln_w), _ptr(ln_b), float(eps), _ptr(gw),
-                              _ptr(gb), _ptr(mask), 1 if gate_on else 0, T, d, _ptr(dx), _ptr(dz), _ptr(out), _ptr(ws), ws_bytes,
+                              _ptr(gb), _ptr(mask), gate_on, T, d, _ptr(dx), _ptr(dz), _ptr(out), _ptr(ws), ws_bytes,
                               _stream(x))
     _lib.check(rc, "smoe_gate_ln_bwd")
     return dx, out[:d], out[d:2 * d], out[2 * d:3 * d], out[3 * d:3 * d + 1], dz
 
 
 def skip_gate_bwd(xn: torch.Tensor, g_f: torch.Tensor, g_out: Optional[torch.Tensor], gate_w: torch.Tensor,
-                  gate_b: Optional[torch.Tensor], mask: Optional[torch.Tensor], gate_on: bool = True):
-    """Backward of one gated half of the residual-MoE block in training (smoe_skip_gate_bwd): (dxn f32 [T,d], dz f32 [T])."""
+                  gate_b: Optional[torch.Tensor], mask: Optional[torch.Tensor], gate_on=True):
+    """Backward of one gated half of the residual-MoE block in training (smoe_skip_gate_bwd): (dxn f32 [T,d], dz f32 [T]).
+    ``gate_on`` as in gate_ln_bwd (2 = the soft gate)."""
+    gate_on = _gate_mode(gate_on)
     _chk(xn, "xn", torch.float32, 2)
     _chk(g_f, "g_f", ndim=2)
     T, d = xn.shape
@@ -498,7 +564,7 @@ def skip_gate_bwd(xn: torch.Tensor, g_f: torch.Tensor, g_out: Optional[torch.Ten
     dxn = torch.empty_like(xn)
     dz = torch.empty(T, dtype=torch.float32, device=xn.device)
     rc = _lib.load().smoe_skip_gate_bwd(_ptr(xn), _ptr(g_f), dtype_code(g_f.dtype), _ptr(g_out), _ptr(gw), _ptr(gb), _ptr(mask),
-                                        1 if gate_on else 0, T, d, _ptr(dxn), _ptr(dz), _stream(xn))
+                                        gate_on, T, d, _ptr(dxn), _ptr(dz), _stream(xn))
     _lib.check(rc, "smoe_skip_gate_bwd")
     return dxn, dz
 

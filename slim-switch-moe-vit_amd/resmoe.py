@@ -53,6 +53,9 @@ class Gate(nn.Module):
       logit, mask, device-side skip counter) -- or none at all inside ``forward_residule_moe``'s fused path, where the
       gate rides on the LayerNorm / router pass;
     * the hard masks are exactly 0 / 1 in value; training keeps the straight-through estimator through ``p``;
+    * ``is_hard=False`` (training only; eval decides hard) is the reference's soft relaxation, mask = (1 - p, p): inside
+      ``forward_residule_moe`` under fp16 autocast it runs on own kernels too (ops.soft_gate_ln forward, gate_on = 2 backward);
+      called on its own, ``forward`` keeps the differentiable torch composition below.  Its counter grows by round(sum(1 - p));
     * ``_skipped_tokens`` accumulates on the device and is read back only when somebody looks at it (the reference
       synchronises the stream twice per block with ``.item()``, resMoE.py:83); ``step`` anneals on the device too."""
 
@@ -166,18 +169,28 @@ class _GateLNFn(th.autograd.Function):
     operand image for the attention half / the masked f32 image the MoE router reads); backward: ONE pass too
     (smoe_gate_ln_bwd: straight-through estimator d m1 / d p = -1, d m0 / d p = +1 with p, xn recomputed from x; LayerNorm backward;
     the gate's and the LayerNorm's parameter gradients).  The
-    caller computes out = f(tk) + xn (the reference's f(tk) + tk + skip_tk in value; the mask gradients are this Function's)."""
+    caller computes out = f(tk) + xn (the reference's f(tk) + tk + skip_tk in value; the mask gradients are this Function's).
+
+    ``soft`` (an enabled ``Gate(is_hard=False)`` in training, resMoE.py:72-74: m = (1 - p, p), no decision, no straight-through
+    estimator): forward ONE pass of smoe_soft_gate_ln_fwd, tk = xn * p, mask = (1 - p, p); backward the same ONE pass with
+    gate_on = 2: d L / d p = +<d_tk, xn> (the opposite sign of the straight-through path; the residual's two terms cancel here too),
+    dxn = d_tk * p + d_xn + dz * gate_w.  The residual is xn itself here as well: the reference's literal sum xn p + xn (1 - p) differs
+    from it by at most two f32 roundings per element."""
 
     @staticmethod
-    def forward(ctx, x, ln_w, ln_b, gate_w, gate_b, eps, thr, skip_count, want16):
-        r = ops.gate_ln_router(x, gate_w, gate_b, thr, ln=(ln_w.detach().float(), ln_b.detach().float() if ln_b is not None else None, eps),
-                               xn16_dtype=th.float16 if want16 else None, want_xn32=True, want_mask=True, skip_count=skip_count,
-                               want_tk32=not want16)
+    def forward(ctx, x, ln_w, ln_b, gate_w, gate_b, eps, thr, skip_count, want16, soft=False):
+        ln = (ln_w.detach().float(), ln_b.detach().float() if ln_b is not None else None, eps)
+        if soft:
+            r = ops.soft_gate_ln(x, gate_w, gate_b, ln=ln, xn16_dtype=th.float16 if want16 else None, want_xn32=True, want_mask=True,
+                                 skip_count=skip_count, want_tk32=not want16)
+        else:
+            r = ops.gate_ln_router(x, gate_w, gate_b, thr, ln=ln, xn16_dtype=th.float16 if want16 else None, want_xn32=True,
+                                   want_mask=True, skip_count=skip_count, want_tk32=not want16)
         xn, mask = r["xn32"], r["mask"]
         # the masked operand image: 16-bit rows for the attention half; the f32 image with the skipped rows zeroed -- what the MoE's
         # router and scatter read -- for the MoE half (a second f32 store of the same pass)
         tk = r["xn16"] if want16 else r["tk32"]
-        ctx.eps, ctx.gate_on = eps, thr is not None
+        ctx.eps, ctx.gate_on = eps, (2 if soft else int(thr is not None))
         ctx.save_for_backward(x, ln_w, gate_w, gate_b if gate_b is not None else th.empty(0, device=x.device), mask,
                               ln_b if ln_b is not None else th.empty(0, device=x.device))
         ctx.has_gb, ctx.has_lb = gate_b is not None, ln_b is not None
@@ -189,7 +202,7 @@ class _GateLNFn(th.autograd.Function):
     def backward(ctx, d_xn, d_tk, _d_mask):
         x, ln_w, gate_w, gate_b, mask, ln_b = ctx.saved_tensors
         if d_tk is None and d_xn is None:
-            return (None,) * 9
+            return (None,) * 10
         if d_tk is None:
             d_tk = th.zeros_like(x)
         d_tk = d_tk.contiguous()
@@ -205,19 +218,19 @@ class _GateLNFn(th.autograd.Function):
             dgb = dgb.reshape(gate_b.shape).to(gate_b.dtype) if ctx.has_gb else None
         else:
             dgw = dgb = None
-        return dx, dg.to(ln_w.dtype), (dbeta if ctx.has_lb else None), dgw, dgb, None, None, None, None
+        return dx, dg.to(ln_w.dtype), (dbeta if ctx.has_lb else None), dgw, dgb, None, None, None, None, None
 
 
 def _train_ok(blk, x) -> bool:
-    """fp16-autocast TRAINING of the residual-MoE block on the library's kernels: hard gates without dropout (the reference's
-    construction, resMoE.py:163-170), LayerNorms / attention / MoE operator the training kernels cover, own stochastic depth."""
+    """fp16-autocast TRAINING of the residual-MoE block on the library's kernels: hard or soft gates without dropout (the reference's
+    construction, resMoE.py:163-170, and its ``is_hard=False``), LayerNorms / attention / MoE operator the training kernels cover,
+    own stochastic depth."""
     from . import dense
     from .vit import Attention, DropPath
     d = x.shape[-1]
     if not (x.is_cuda and x.dim() == 3 and x.dtype == th.float32 and x.is_contiguous() and dense.autocast_half_training(x)):
         return False
-    gates_ok = all(isinstance(g, Gate) and (g.is_hard or not g.training) and not (g.training and g.head[0].p > 0)
-                   for g in (blk.dense_gate, blk.moe_gate))
+    gates_ok = all(isinstance(g, Gate) and not (g.training and g.head[0].p > 0) for g in (blk.dense_gate, blk.moe_gate))
     return (gates_ok and isinstance(blk.attn, Attention) and (blk.stochastic_depth_inactive() or isinstance(blk.drop_path, DropPath))
             and all(dense.layer_norm_supported(x, n) for n in (blk.norm1, blk.norm2))
             and getattr(blk.mlp, "forward_add", None) is not None and ops.gate_ln_router_supported(d, 0, 1))
@@ -231,24 +244,31 @@ def _gate_ln(x2, norm, gate):
     return norm.weight, norm.bias, lin.weight, lin.bias, norm.eps, thr, (gate.skip_counter(x2.device) if thr is not None else None)
 
 
+def _soft(gate) -> bool:
+    """Whether this gate takes the soft branch right now (resMoE.py:72: in training only, and not while it is disabled)."""
+    return gate.training and not gate.is_hard and not gate.disable
+
+
 def _residual_block_train(blk, x):
     """models/resMoE.py:126-145 in fp16-autocast training, forward and backward on the library's kernels: per half ONE pass for
     LayerNorm + gate (+ the masked operand image), the operator's own training path (qkv / attention / projection GEMMs with the
     normed residual -- and stochastic depth's per-row factor -- in the projection's store; the MoE operator with the residual in
     its combine), and in the backward the gate's straight-through gradients fused with the gradient of the residual in one pass in
-    front of the LayerNorm backward kernel.  Preconditions: _train_ok."""
+    front of the LayerNorm backward kernel.  Each gate chooses its mode on its own: a soft one (_soft) hands the operator xn * p
+    instead of the masked rows, and a soft moe_gate skips nothing -- every row is dispatched (zero_rows=None).  Preconditions: _train_ok."""
     B, N, d = x.shape
     x2 = x.reshape(B * N, d)
     _, rows1 = blk._depth_scale(x)
-    xn, tk16, _ = _GateLNFn.apply(x2, *_gate_ln(x2, blk.norm1, blk.dense_gate), True)
+    xn, tk16, _ = _GateLNFn.apply(x2, *_gate_ln(x2, blk.norm1, blk.dense_gate), True, _soft(blk.dense_gate))
     a, added = blk.attn(tk16.reshape(B, N, d), residual=xn.reshape(B, N, d), row_scale=rows1)
     if not added:   # (the projection could not take the residual: add it here; the gate gradients are unaffected)
         a = xn.reshape(B, N, d) + (a if rows1 is None else a * rows1.reshape(B, N, 1).to(a.dtype))
     x1 = a.reshape(B * N, d)
     _, rows2 = blk._depth_scale(x)
-    xn2, tk32, mask2 = _GateLNFn.apply(x1, *_gate_ln(x1, blk.norm2, blk.moe_gate), False)
+    soft2 = _soft(blk.moe_gate)
+    xn2, tk32, mask2 = _GateLNFn.apply(x1, *_gate_ln(x1, blk.norm2, blk.moe_gate), False, soft2)
     # (the skipped tokens' all-zero rows get row groups of their own in the operator's training path: autograd._route_train)
-    skipped = mask2[:, 0] > 0.5 if blk.moe_gate.active_threshold() is not None else None
+    skipped = mask2[:, 0] > 0.5 if blk.moe_gate.active_threshold() is not None and not soft2 else None
     return blk.mlp.forward_add(tk32.reshape(B, N, d), xn2.reshape(B, N, d), row_scale=rows2, zero_rows=skipped)
 
 
@@ -307,16 +327,17 @@ def forward_residule_moe(self, x):
 
 def patch_blocks_with_moe(model: VisionTransformer, num_experts: int, top_k: int, residual: bool,
                           starting_threshold: float = 1.0, target_threshold: float = 0.9, drop_rate: float = 0.0,
-                          mlp_ratio: int = 4, **moe_kwargs):
-    """What the reference factories do to every Block (resMoE.py:163-186 / 200-208)."""
+                          mlp_ratio: int = 4, is_hard: bool = True, **moe_kwargs):
+    """What the reference factories do to every Block (resMoE.py:163-186 / 200-208).  ``is_hard`` is handed to every ``Gate`` (the
+    reference's factories leave it at the constructor's default, True, and users set the attribute by hand: that keeps working)."""
     embed_dim = model.embed_dim
     for _, module in model.named_modules():
         if isinstance(module, Block):
             if residual:
                 module.dense_gate = Gate(embed_dim, 1.0, starting_threshold=starting_threshold,
-                                         target_threshold=target_threshold)
+                                         target_threshold=target_threshold, is_hard=is_hard)
                 module.moe_gate = Gate(embed_dim, 1.0, starting_threshold=starting_threshold,
-                                       target_threshold=target_threshold)
+                                       target_threshold=target_threshold, is_hard=is_hard)
             module.mlp = CustomizedMoEMLP(embed_dim, embed_dim * mlp_ratio, moe_num_experts=num_experts,
                                           moe_top_k=top_k, drop=drop_rate, **moe_kwargs)
             if residual:
@@ -331,11 +352,12 @@ def _split_moe_kwargs(kwargs):
 
 
 @register_model
-def resmoe_tiny_patch16_224_expert8(pretrained=False, starting_threshold=1.0, target_threshold=0.9, **kwargs):
-    """models/resMoE.py:151-187 (DeiT-Tiny, E=8, top-2, token-skip gates)."""
+def resmoe_tiny_patch16_224_expert8(pretrained=False, starting_threshold=1.0, target_threshold=0.9, gate_is_hard=True, **kwargs):
+    """models/resMoE.py:151-187 (DeiT-Tiny, E=8, top-2, token-skip gates).  ``gate_is_hard=False`` (this build's keyword) builds
+    every ``Gate`` with ``is_hard=False``: the soft relaxation in training."""
     moe_kwargs = _split_moe_kwargs(kwargs)
     model = deit_tiny_patch16_224(pretrained=pretrained, **kwargs)
-    return patch_blocks_with_moe(model, 8, 2, True, starting_threshold, target_threshold, **moe_kwargs)
+    return patch_blocks_with_moe(model, 8, 2, True, starting_threshold, target_threshold, is_hard=gate_is_hard, **moe_kwargs)
 
 
 @register_model
@@ -365,12 +387,12 @@ def moe_base_patch16_224_expert8_top1(pretrained=False, **kwargs):
 
 
 @register_model
-def resmoe_base_patch16_224_expert8_top1(pretrained=False, starting_threshold=1.0, target_threshold=0.9, **kwargs):
+def resmoe_base_patch16_224_expert8_top1(pretrained=False, starting_threshold=1.0, target_threshold=0.9, gate_is_hard=True, **kwargs):
     """ViT-B/16, E=8, top-1, with the token-skip gates and residual-on-normed forward."""
     moe_kwargs = _split_moe_kwargs(kwargs)
     model = _deit(768, 12, 12, pretrained=pretrained, **kwargs)
     return patch_blocks_with_moe(model, 8 // moe_kwargs.get("world_size", 1), 1, True, starting_threshold,
-                                 target_threshold, **moe_kwargs)
+                                 target_threshold, is_hard=gate_is_hard, **moe_kwargs)
 
 
 @register_model

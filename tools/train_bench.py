@@ -6,6 +6,7 @@ model name: default moe_base_patch16_224_expert8_top1 with the SwitchGate (cfg 5
 (token-skip gates, residual on the normed activations, naive gate; thresholds set so that ~40 % of the tokens skip).
 TRAIN_BENCH_EP=static|counted (model mode): the step through the EXPERT-PARALLEL code path on a one-rank RCCL group -- cfg 5's capacity
 gate on the static exchange (fixed slots, counts in-band, no host round trip) or on the counted one (a count read-back per layer).
+TRAIN_BENCH_SOFT_GATES=1 (resmoe_* names): the model is built with soft gates (gate_is_hard=False: skip_tk = 1 - p, tk = p in training).
 image size: the fifth argument, else the `_<size>_` / `_<size>` field of the model name (moe_large_patch16_384_* -> 384), else 224."""
 import os, re, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,7 +71,8 @@ else:
     m_size = re.search(r"patch\d+_(\d+)(?:_|$)", name)
     size = int(sys.argv[5]) if len(sys.argv) > 5 else (int(m_size.group(1)) if m_size else 224)
     if name.startswith("resmoe"):
-        model = sm.create_model(name, num_classes=1000, drop_path_rate=0.1, starting_threshold=0.55, target_threshold=0.5)
+        soft = {"gate_is_hard": False} if os.environ.get("TRAIN_BENCH_SOFT_GATES") else {}
+        model = sm.create_model(name, num_classes=1000, drop_path_rate=0.1, starting_threshold=0.55, target_threshold=0.5, **soft)
         with torch.no_grad():
             for n, p in model.named_parameters():
                 if "_gate.head.1.weight" in n:
@@ -179,7 +181,7 @@ else:
     gates = [m for m in model.modules() if isinstance(m, sm.Gate)]
     extra = ""
     if gates:
-        extra = f"; skipped tokens {sum(gt._skipped_tokens for gt in gates) / max(1, sum(gt._total_tokens for gt in gates)):.2f}"
+        extra = f"; {'soft gates, ' if not gates[0].is_hard else ''}skipped tokens {sum(gt._skipped_tokens for gt in gates) / max(1, sum(gt._total_tokens for gt in gates)):.2f}"
     print(f"{name} train step (fwd + bwd + clip + AdamW), batch {images}: {t:.2f} ms = {images / t * 1e3:.0f} images/s{extra}", flush=True)
 
     if os.environ.get("TRAIN_BENCH_TRACE"):
