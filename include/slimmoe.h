@@ -432,6 +432,28 @@ int smoe_switch_gate_bwd(const float* probs, const int64_t* idx, const float* ds
 size_t smoe_switch_aux_workspace_bytes(int64_t T, int E);
 int smoe_switch_aux(const float* probs, const int32_t* counts, int64_t T, int E, float* aux, float* coef, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* GShard gate (fmoe.gates.GShardGate; the rule is restated in INTEGRATION.md), behind the NAIVE top-2 router.  E <= 256.
+ * smoe_gshard_prune: idx int64 [T, 2] (the router's; ids outside [0, E) read as -1), score f32 [T, 2], u f32 [T] or NULL ->
+ *   idx_out int64 [T, 2] and top1_counts i32 [E] = #{t : idx[t, 0] == e}.  Capacity first, in flat order: entry i = 2 t + j is kept
+ *   while fewer than `capacity` entries i' < i named the same expert (capacity < 0: no clamp); then random routing: a second choice
+ *   with 2 score[t, 1] < u[t] (f32 compare) becomes -1 and has still used its capacity slot.  Two launches (chunk histograms; ranks
+ *   by wave ballots), deterministic.  ceil(2 T / 1024) * E <= 2^20.
+ * smoe_gshard_aux: logits f32 [T, E] -> aux [1] = mean_e(c_e m_e) num_expert^2 with c_e = top1_counts[e] / T and
+ *   m_e = mean_t softmax(logits[t, :])[e] (f32), and coef [E] = num_expert^2 top1_counts[e] / (E T^2) = d aux / d softmax[t, e] for
+ *   every t.  num_expert = the local expert count (it divides E).  Two launches: column sums per 256-row chunk, then one workgroup
+ *   adds the chunks in order -- no float atomics, bit-reproducible.
+ * smoe_gshard_gate_bwd: one pass, p = softmax(logits[t, :]) recomputed:
+ *   dlogits[t, e] = s p[e] (coef[e] - sum_j p[j] coef[j]) + [e == idx[t, a]] score_a (ds_a - (score_0 ds_0 + score_1 ds_1)), a = 0, 1,
+ *   s = *coef_scale (device scalar: d loss / d aux; NULL = 1), coef NULL = no balance-loss term, ds_a = dscore[t, a], taken as 0 where
+ *   idx_out[t, a] < 0 (whatever the buffer holds) and everywhere when dscore is NULL.                                            */
+size_t smoe_gshard_prune_workspace_bytes(int64_t T, int E);
+int smoe_gshard_prune(const int64_t* idx, const float* score, const float* u, int64_t T, int E, int64_t capacity, int64_t* idx_out,
+                      int32_t* top1_counts, void* workspace, size_t workspace_bytes, void* stream);
+size_t smoe_gshard_aux_workspace_bytes(int64_t T, int E);
+int smoe_gshard_aux(const float* logits, const int32_t* top1_counts, int64_t T, int E, int num_expert, float* aux, float* coef,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int smoe_gshard_gate_bwd(const float* logits, const int64_t* idx, const int64_t* idx_out, const float* score, const float* dscore,
+                         const float* coef, const float* coef_scale, int64_t T, int E, float* dlogits, void* stream);
 /* smoe_transpose_cast: dst[b][c][r] = (dst_dtype) src[b][r][c] for b < B; R % 64 == 0, C % 64 == 0.  The backward pass reads every
  * expert weight [E, out, in] a second time as [E, in, out] (FastMoE: `MOELinear.backward` -> fmoe_cuda.linear_backward contracts
  * grad_out with the weight over `out`); this makes that 16-bit image straight from the f32 master in one pass.               */

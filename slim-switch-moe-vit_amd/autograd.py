@@ -301,6 +301,30 @@ class _SwitchScoreAux(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+class _GShardScoreAux(torch.autograd.Function):
+    """GShardGate's differentiable outputs from what the HIP router already computed: score = softmax over the two chosen logits and
+    the balance loss aux = mean_e(c_e m_e) num_expert^2 (fmoe.gates.GShardGate).  Forward: the router's score, and
+    smoe_gshard_aux for aux.  Backward: ONE pass over [T, E] (smoe_gshard_gate_bwd); the score gradient of an entry the prune dropped
+    counts as zero."""
+
+    @staticmethod
+    def forward(ctx, logits, score, idx, idx_out, top1, num_expert):
+        aux, coef = ops.gshard_aux(logits, top1, num_expert)
+        ctx.save_for_backward(logits, score, idx, idx_out, coef)
+        ctx.set_materialize_grads(False)     # no aux loss in the objective: daux is None, not a zero tensor
+        return score.view_as(score), aux
+
+    @staticmethod
+    def backward(ctx, dscore, daux):
+        logits, score, idx, idx_out, coef = ctx.saved_tensors
+        if dscore is None and daux is None:
+            return (None,) * 6
+        ds = dscore.to(torch.float32).contiguous() if dscore is not None else None
+        scale = daux.reshape(1).to(torch.float32) if daux is not None else None      # multiplied onto coef inside the kernel
+        return (ops.gshard_gate_bwd(logits, idx, idx_out, score, ds, coef if daux is not None else None, scale),
+                None, None, None, None, None)
+
+
 def _zero_row_routing(mod):
     """(int64 [k] (device): the experts an all-zero row is routed to (top-k of the gate bias; ties -> lowest id), from the HIP
     router itself; the group -> expert map i32 [E + k]; the zero groups' ids int64 [1, k]), cached per version of the gate parameters."""
@@ -335,12 +359,13 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
     groups' weight gradients are rank-1 (_GroupFFN.backward).
     ``slots`` (dict with "tab": ep._SlotTable, "agreed": rows the table was agreed for): the plan in the slot layout of the static
     expert exchange (smoe_dispatch_plan_slots: pos has tab.rows entries, S is the send buffer); "counts" / "raw" come back in it."""
-    from .fmoe import SwitchGate
+    from .fmoe import GShardGate, SwitchGate
 
     g = mod.gate
     k = mod.top_k
     T = x.shape[0]
     is_switch = isinstance(g, SwitchGate)
+    is_gshard = isinstance(g, GShardGate)
     noise = g.make_noise(T, x.device) if is_switch else None
     gw = g.gate.weight.detach().float().contiguous()
     gb = g.gate.bias.detach().float() if g.gate.bias is not None else None
@@ -351,23 +376,28 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
                                                           want_probs=is_switch)
         cap = g.capacity(T)
         E = g.tot_expert
+        plan_idx, plan_cap = idx, cap
+        if is_gshard:   # capacity + random routing on the gate's own kernels; the plan over what is left has no capacity of its own
+            (idx_out, top1), plan_cap = g.prune(idx, score_c), -1
+            plan_idx = idx_out
         if slots is not None:
             tab, agreed = slots["tab"], slots["agreed"]
             if T <= agreed:
-                counts, offsets, _gend, pos, inv_pos, pruned, raw = ops.dispatch_plan_slots(idx, E, tab.base_dev, tab.rows, cap)
+                counts, offsets, _gend, pos, inv_pos, pruned, raw = ops.dispatch_plan_slots(plan_idx, E, tab.base_dev, tab.rows, plan_cap)
             else:   # over the agreed size: the buffers keep their shape (the peers must not hang); reported by the overflow watch
-                counts, offsets, _gend, pos, inv_h, _pr, raw = ops.dispatch_plan_slots(idx[:agreed].contiguous(), E, tab.base_dev,
-                                                                                      tab.rows, cap)
+                counts, offsets, _gend, pos, inv_h, _pr, raw = ops.dispatch_plan_slots(plan_idx[:agreed].contiguous(), E, tab.base_dev,
+                                                                                      tab.rows, plan_cap)
                 inv_pos = torch.full((T * k,), -1, dtype=torch.int64, device=x.device)
                 inv_pos[: agreed * k].copy_(inv_h)
             slots["counts"], slots["raw"] = counts, raw
-        elif zero_rows is not None and not is_switch and cap < 0 and E + k <= 63:
+        elif zero_rows is not None and not is_switch and not is_gshard and cap < 0 and E + k <= 63:
+            # (not for a GShardGate without a capacity: its plan runs over the pruned ids -- random routing still drops entries)
             _idx0, g_map, zero_ids = _zero_row_routing(mod)                                # (cached per gate-parameter version)
             idx_plan = torch.where(zero_rows.reshape(T, 1), zero_ids, idx)
             counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx_plan, E + k, cap)
             zero_groups = k
         else:
-            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, E, cap)
+            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(plan_idx, E, plan_cap)
     mod.last_plan = (idx, score_c, counts, offsets, pos, inv_pos)
     S = None
     if need_grad:  # tiny [T,E] work -- the routing itself stays the HIP router's
@@ -379,6 +409,9 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
             logits = _GateLogits.apply(x, g.gate.weight, g.gate.bias, logits_r)
         if is_switch:   # probs_r = softmax(logits + noise) and score_c = probs_r[idx] are the router's own
             score, aux = _SwitchScoreAux.apply(logits, probs_r, score_c, idx, counts, g.tot_expert)
+            g.set_loss(aux)
+        elif is_gshard:  # score_c = softmax over the two chosen logits is the router's own; aux from the logits and the first choices
+            score, aux = _GShardScoreAux.apply(logits, score_c, idx, idx_out, top1, g.num_expert)
             g.set_loss(aux)
         else:
             score = torch.softmax(logits.gather(1, idx), dim=-1)

@@ -669,7 +669,7 @@ def _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, n
     than its slot, keeps the agreed buffer shape (it drops what does not fit; its peers must not hang) and the violation is raised
     on every rank by check_static_overflow -- never here, by this rank alone."""
     from . import ops
-    from .fmoe import SwitchGate
+    from .fmoe import GShardGate, SwitchGate
 
     g = mod.gate
     W, E_local, k, d = mod.world_size, mod.num_expert, mod.top_k, mod.d_model
@@ -682,6 +682,8 @@ def _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, n
     counts = raw = None
     if T > 0:
         cap = g.capacity(T) if kind == "capacity" else -1               # (on top of the slots: what THIS batch may keep)
+        if isinstance(g, GShardGate):
+            cap = -1                                                    # (plan_idx is the gate's own pruned ids: already within it)
         if T <= agreed:
             counts, offsets, gend, pos, inv_pos, pruned, raw = ops.dispatch_plan_slots(plan_idx, E_tot, tab.base_dev, tab.rows, cap)
         else:
@@ -766,7 +768,7 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
     ONE pass) the routing is taken as given: ``idx`` / ``score`` [T, k], ``idx_plan`` (= idx, -1 for the tokens the skip gate
     masked: they are simply not sent), ``src`` = the 16-bit operand image the send buffers are gathered from."""
     from . import ops
-    from .fmoe import SwitchGate
+    from .fmoe import GShardGate, SwitchGate
 
     g = mod.gate
     W, E_local, k, d = mod.world_size, mod.num_expert, mod.top_k, mod.d_model
@@ -802,6 +804,17 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
         idx, score, _, probs = ops.router_topk(x, gw, gb, k, g.kind, noise, want_probs=isinstance(g, SwitchGate))
     if plan_idx is None:
         plan_idx = idx
+    if isinstance(g, GShardGate):
+        # capacity (per source rank, on this rank's T rows) + random routing on the gate's own kernels: every plan below runs over
+        # what is left, without a capacity of its own.  `cap` keeps deciding what a capacity gate decides (one chunk, static exchange).
+        if routed is not None:    # (a caller's idx_plan -- the skip gate's -1 entries -- would be lost under the prune below)
+            raise NotImplementedError("ep_forward_steps: a GShardGate takes no pre-routed batch (norm_gate_fusable is the NaiveGate's)")
+        g.set_loss(None)
+        if T > 0:
+            plan_idx = g.prune(idx, score)[0]
+        plan_cap = -1
+    else:
+        plan_cap = cap
     kind = static_kind(mod, cd)
     if kind is not None:
         # decided from the configuration and the AGREED row count only: every rank takes the same branch whatever its batch
@@ -810,7 +823,7 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
             return (yield from _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, next_norm, agreed, kind))
     plans = []
     for (t0, t1) in bounds:
-        plans.append(ops.dispatch_plan(plan_idx[t0:t1], g.tot_expert, cap))
+        plans.append(ops.dispatch_plan(plan_idx[t0:t1], g.tot_expert, plan_cap))
     mod.last_plan = (idx, score) + tuple(plans[0][:4])
     if isinstance(g, SwitchGate):
         from .autograd import switch_aux_loss

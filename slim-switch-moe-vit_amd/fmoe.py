@@ -151,6 +151,48 @@ class SwitchGate(NaiveGate):
         return torch.empty(T, self.tot_expert, device=device).uniform_(1.0 - self.switch_eps, 1.0 + self.switch_eps)
 
 
+class GShardGate(NaiveGate):
+    """GShard top-2 gate with a per-expert capacity, the GShard balance loss and random routing of the second choice
+    (fmoe.gates.GShardGate; the rule is restated in INTEGRATION.md).  The routing is the naive top-2 router's; this gate's own
+    arithmetic runs behind it on smoe_gshard_prune / _aux / _gate_bwd.
+
+    ``capacity`` = (train, eval) rates or one rate for both: cap = (ceil(rate * T_local) * 2) // E_total entries per expert, applied
+    per source rank in flat order (entry 2 t + j).  ``random_routing``: the second choice of token t is dropped when
+    2 * score[t, 1] < u[t], u ~ U[0, 1) -- in training AND in eval, as upstream; pass False for a deterministic gate."""
+
+    kind = ops.GATE_NAIVE
+
+    def __init__(self, d_model: int, num_expert: int, world_size: int, topk: int = 2, capacity=(1.2, 2.4),
+                 random_routing: bool = True, gate_bias: bool = True):
+        assert topk == 2, "GShardGate is top-2"
+        super().__init__(d_model, num_expert, world_size, top_k=2)
+        if not gate_bias:
+            self.gate = nn.Linear(d_model, self.tot_expert, bias=False)
+        self.capacity_factor = capacity
+        self.random_routing = random_routing
+        self.last_routing = None  # (u | None, idx_out, top1_counts) of the latest forward, for inspection
+
+    def capacity(self, n_tokens: int) -> int:
+        cf = self.capacity_factor
+        if cf is None:
+            return -1
+        if isinstance(cf, (tuple, list)):
+            cf = cf[0] if self.training else cf[1]
+        return (int(math.ceil(cf * n_tokens)) * self.top_k) // self.tot_expert
+
+    def make_uniform(self, T: int, device) -> Optional[torch.Tensor]:
+        return torch.rand(T, device=device) if self.random_routing else None
+
+    def prune(self, idx: torch.Tensor, score: torch.Tensor):
+        """(idx_out, top1_counts) for the router's ``idx`` / ``score`` [T, 2]: capacity, then random routing (ops.gshard_prune).  The
+        dispatch plan then runs over ``idx_out`` without a capacity of its own."""
+        T = idx.shape[0]
+        u = self.make_uniform(T, idx.device)
+        idx_out, top1 = ops.gshard_prune(idx, score, u, self.tot_expert, self.capacity(T))
+        self.last_routing = (u, idx_out, top1)
+        return idx_out, top1
+
+
 class _Expert(nn.Module):
     """fmoe.transformer._Expert: htoh4 -> activation -> h4toh over expert-sorted rows.
 
@@ -225,7 +267,7 @@ class FMoETransformerMLP(nn.Module):
 
     forward(x[..., d]) -> same shape:  router -> dispatch plan -> token scatter -> grouped GEMM (+bias,
     +GELU) -> grouped GEMM (+bias) -> gather/combine, all HIP kernels.
-    Keyword-only extensions with reference defaults: ``gate`` ("naive" | "switch" | a gate class),
+    Keyword-only extensions with reference defaults: ``gate`` ("naive" | "switch" | "gshard" | a gate class),
     ``capacity_factor``, ``world_size`` / ``moe_group`` (expert parallel), ``compute_dtype``.
     """
 
@@ -245,6 +287,9 @@ class FMoETransformerMLP(nn.Module):
             elif gate == "switch":
                 cap = capacity_factor if capacity_factor is not None else (1.2, 2.4)
                 self.gate = SwitchGate(d_model, num_expert, world_size, top_k, capacity=cap, capacity_mode=capacity_mode)
+            elif gate == "gshard":
+                cap = capacity_factor if capacity_factor is not None else (1.2, 2.4)
+                self.gate = GShardGate(d_model, num_expert, world_size, top_k, capacity=cap)
             else:
                 raise ValueError(f"unknown gate {gate!r}")
         else:
@@ -352,11 +397,18 @@ class FMoETransformerMLP(nn.Module):
         if tail is not None and cap < 0 and tail[0] > 0 and T % tail[0] == 0 and 0 < tail[1] < tail[0]:
             sub = (int(tail[0]), int(tail[1]))
         # the router pass also counts for the plan (count_by_gate folded in) -- over all rows: of no use to a plan over some
-        hist = ops.chunk_hist(T, d, g.tot_expert, k, x2.device) if sub is None else None
+        # (not for a GShardGate: its plan runs over the pruned ids, which the router has not seen)
+        is_gshard = isinstance(g, GShardGate)
+        hist = ops.chunk_hist(T, d, g.tot_expert, k, x2.device) if sub is None and not is_gshard else None
         xn16, _, idx, score, _, probs = ops.ln_router_topk(
             x2, norm.weight.detach().float(), norm.bias.detach().float() if norm.bias is not None else None, norm.eps,
             gw, gb, k, g.kind, noise, xn16_dtype=cd, want_probs=is_switch, hist=hist)
-        counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap, hist=hist, subset=sub)
+        if is_gshard:     # capacity + random routing on the gate's own kernels; the plan over what is left has no capacity of its own
+            g.set_loss(None)
+            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(g.prune(idx, score)[0], g.tot_expert, -1, want_pruned=False,
+                                                                      subset=sub)
+        else:
+            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap, hist=hist, subset=sub)
         self.last_plan = (idx, score, counts, offsets, pos, inv_pos)
         if is_switch:
             from .autograd import switch_aux_loss
@@ -531,6 +583,11 @@ class FMoETransformerMLP(nn.Module):
         if gw.dtype != torch.float32:
             gw, gb = gw.float(), (gb.float() if gb is not None else None)
         idx, score, _, probs = ops.router_topk(x, gw.contiguous(), gb, g.top_k, g.kind, noise, want_probs=want_probs)
+        if isinstance(g, GShardGate):   # capacity + random routing on the gate's own kernels, then a plan without a capacity
+            g.set_loss(None)            # (no balance loss in a no-grad forward: nothing reads it, and it would cost a logits store)
+            idx_out, _ = g.prune(idx, score)
+            counts, offsets, pos, inv_pos, _ = ops.dispatch_plan(idx_out, g.tot_expert, -1)
+            return idx, score, probs, counts, offsets, pos, inv_pos, idx_out
         cap = g.capacity(T)
         counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap)
         return idx, score, probs, counts, offsets, pos, inv_pos, pruned

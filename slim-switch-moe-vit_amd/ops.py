@@ -1114,6 +1114,86 @@ def switch_gate_bwd(probs: torch.Tensor, idx: torch.Tensor, dscore: Optional[tor
     return out
 
 
+def _gshard_pairs(t: torch.Tensor, name: str, dtype, T: Optional[int] = None) -> int:
+    """``t`` is a contiguous [T, 2] tensor of ``dtype`` (the top-2 router's layout); returns T."""
+    _chk(t, name, dtype, align=8 if dtype == torch.int64 else 4)
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise RuntimeError(f"{name}: expected [T, 2] (the GShard gate is top-2), got {tuple(t.shape)}")
+    if T is not None and t.shape[0] != T:
+        raise RuntimeError(f"{name}: expected {T} rows, got {t.shape[0]}")
+    return t.shape[0]
+
+
+def gshard_prune(idx: torch.Tensor, score: torch.Tensor, u: Optional[torch.Tensor], E: int, capacity: int = -1):
+    """(idx_out i64 [T, 2], top1_counts i32 [E]): the GShard gate's capacity and random routing on the top-2 router's ``idx`` /
+    ``score`` [T, 2] (smoe_gshard_prune).  Entry 2 t + j is kept while fewer than ``capacity`` earlier flat entries named its expert
+    (< 0: no clamp); then, with ``u`` (f32 [T]), a second choice with 2 score[t, 1] < u[t] is dropped.  Dropped entries are -1;
+    top1_counts[e] counts the first choices before any drop.  Two launches."""
+    T = _gshard_pairs(idx, "idx", torch.int64)
+    _gshard_pairs(score, "score", torch.float32, T)
+    if u is not None:
+        _chk(u, "u", torch.float32, 1, align=4)
+        if u.numel() != T:
+            raise RuntimeError(f"u: expected {T} entries, got {u.numel()}")
+    dev = idx.device
+    lib = _lib.load()
+    ws_bytes = lib.smoe_gshard_prune_workspace_bytes(T, int(E))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    idx_out = torch.empty_like(idx)
+    top1 = torch.empty(int(E), dtype=torch.int32, device=dev)
+    with _timed("gshard_prune", {"bytes": T * 44}, idx):
+        rc = lib.smoe_gshard_prune(_ptr(idx), _ptr(score), _ptr(u), T, int(E), int(capacity), _ptr(idx_out), _ptr(top1), _ptr(ws),
+                                   ws_bytes, _stream(idx))
+    _lib.check(rc, "smoe_gshard_prune")
+    return idx_out, top1
+
+
+def gshard_aux(logits: torch.Tensor, top1_counts: torch.Tensor, num_expert: int):
+    """(aux f32 [], coef f32 [E]): the GShard balance loss mean_e(c_e m_e) num_expert^2 from the router's logits [T, E] (row softmax in
+    f32) and the first choices' counts (i32 [E]), and coef[e] = d aux / d softmax(logits)[t, e] -- two launches, bit-reproducible."""
+    _chk(logits, "logits", torch.float32, 2, align=4)
+    _chk(top1_counts, "top1_counts", torch.int32, 1, align=4)
+    T, E = logits.shape
+    if top1_counts.numel() != E:
+        raise RuntimeError("gshard_aux: one count per expert")
+    lib = _lib.load()
+    out = torch.empty(E + 1, dtype=torch.float32, device=logits.device)
+    ws_bytes = lib.smoe_gshard_aux_workspace_bytes(T, E)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=logits.device)
+    with _timed("gshard_aux", {"bytes": 2 * T * E * 4}, logits):
+        rc = lib.smoe_gshard_aux(_ptr(logits), _ptr(top1_counts), T, E, int(num_expert), _ptr(out), out.data_ptr() + 4, _ptr(ws), ws_bytes,
+                                 _stream(logits))
+    _lib.check(rc, "smoe_gshard_aux")
+    return out[0], out[1:]
+
+
+def gshard_gate_bwd(logits: torch.Tensor, idx: torch.Tensor, idx_out: torch.Tensor, score: torch.Tensor,
+                    dscore: Optional[torch.Tensor], coef: Optional[torch.Tensor], coef_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dlogits [T, E] of the GShard gate's score (softmax over the two chosen logits; ``dscore`` [T, 2] counts only where ``idx_out`` >= 0)
+    and balance loss (``coef`` from gshard_aux times ``coef_scale``, a one-element f32 device tensor = d loss / d aux) in one pass."""
+    _chk(logits, "logits", torch.float32, 2, align=4)
+    T, E = logits.shape
+    _gshard_pairs(idx, "idx", torch.int64, T)
+    _gshard_pairs(idx_out, "idx_out", torch.int64, T)
+    _gshard_pairs(score, "score", torch.float32, T)
+    if dscore is not None:
+        _gshard_pairs(dscore, "dscore", torch.float32, T)
+    if coef is not None:
+        _chk(coef, "coef", torch.float32, 1, align=4)
+        if coef.numel() != E:
+            raise RuntimeError("gshard_gate_bwd: one coefficient per expert")
+    if coef_scale is not None:
+        _chk(coef_scale, "coef_scale", torch.float32, align=4)
+        if coef is None or coef_scale.numel() != 1:
+            raise RuntimeError("gshard_gate_bwd: coef_scale is one element and needs coef")
+    out = torch.empty_like(logits)
+    with _timed("gshard_gate_bwd", {"bytes": 2 * T * E * 4 + T * 56}, logits):
+        rc = _lib.load().smoe_gshard_gate_bwd(_ptr(logits), _ptr(idx), _ptr(idx_out), _ptr(score), _ptr(dscore), _ptr(coef),
+                                              _ptr(coef_scale), T, E, _ptr(out), _stream(logits))
+    _lib.check(rc, "smoe_gshard_gate_bwd")
+    return out
+
+
 def pad_offsets(offsets: torch.Tensor) -> torch.Tensor:
     _chk(offsets, "offsets", torch.int32, 1)
     out = torch.empty_like(offsets)
