@@ -454,6 +454,26 @@ int smoe_gshard_aux(const float* logits, const int32_t* top1_counts, int64_t T, 
                     void* workspace, size_t workspace_bytes, void* stream);
 int smoe_gshard_gate_bwd(const float* logits, const int64_t* idx, const int64_t* idx_out, const float* score, const float* dscore,
                          const float* coef, const float* coef_scale, int64_t T, int E, float* dlogits, void* stream);
+/* Noisy top-k gate (fmoe.gates.NoisyGate; the rule is restated in INTEGRATION.md), behind the router run over the [2E, d] image
+ * [w_gate^T ; w_noise^T].  2 <= E <= 32, 1 <= k <= 4, k < E, ceil(T / 256) <= 2^24; anything else is refused before any launch.
+ * smoe_noisy_gate_fwd: logits2 f32 [T, 2E] (columns 0..E-1 clean, E..2E-1 raw), eps f32 [T, E] or NULL (= zero noise) ->
+ *   sigma = softplus(raw) + 1e-2 (torch's softplus: beta 1, threshold 20) when `training`, else 0; noisy = clean + eps sigma;
+ *   v_1 >= .. >= v_{k+1} the k + 1 largest noisy values of the row at experts i_1 .. i_{k+1} (ties -> lowest id; a NaN is never
+ *   chosen, and every id written lies in [0, E));  idx int64 [T, k] = (i_1 .. i_k), score f32 [T, k] = softmax(v_1 .. v_k),
+ *   keep f64 [T, 2] = (v_k, v_{k+1}), next i32 [T] = i_{k+1};  imp [E] = the scores summed at their experts,
+ *   load [E] = sum_t Phi((clean - thr) / sigma), thr = v_{k+1} where noisy > v_{k+1} (strict) else v_k (training; zeros in eval),
+ *   aux [1] = cv2(imp) + cv2(load), cv2(v) = var_unbiased(v) / (mean(v)^2 + 1e-10), coef_imp / coef_load [E] = d aux / d imp_e,
+ *   d aux / d load_e.  Two launches: a row pass leaving column partials per 256-row chunk, a finish pass adding them in chunk
+ *   order -- no float atomics, bit-reproducible.  The arithmetic between the f32 inputs and outputs is f64.
+ * smoe_noisy_gate_bwd: one pass (the scores are recomputed from the kept values' experts) -> dlogits2 f32 [T, 2E] of sum(score dscore) + *coef_scale aux.  dscore f32 [T, k] or NULL (no score
+ *   term); coef_scale (device scalar, d loss / d aux) NULL = the loss is not in the objective: both loss terms are left out.   */
+size_t smoe_noisy_gate_workspace_bytes(int64_t T, int E);
+int smoe_noisy_gate_fwd(const float* logits2, const float* eps, int64_t T, int E, int k, int training, int64_t* idx, float* score,
+                        double* keep, int32_t* next, float* imp, float* load, float* aux, float* coef_imp, float* coef_load,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int smoe_noisy_gate_bwd(const float* logits2, const float* eps, const int64_t* idx, const double* keep, const int32_t* next,
+                        const float* dscore, const float* coef_imp, const float* coef_load,
+                        const float* coef_scale, int64_t T, int E, int k, int training, float* dlogits2, void* stream);
 /* smoe_transpose_cast: dst[b][c][r] = (dst_dtype) src[b][r][c] for b < B; R % 64 == 0, C % 64 == 0.  The backward pass reads every
  * expert weight [E, out, in] a second time as [E, in, out] (FastMoE: `MOELinear.backward` -> fmoe_cuda.linear_backward contracts
  * grad_out with the weight over `out`); this makes that 16-bit image straight from the f32 master in one pass.               */

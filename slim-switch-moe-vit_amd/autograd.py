@@ -325,6 +325,30 @@ class _GShardScoreAux(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+class _NoisyScoreAux(torch.autograd.Function):
+    """NoisyGate's differentiable outputs from what smoe_noisy_gate_fwd already computed behind the router: score = softmax over the
+    k largest noisy values and aux = cv2(importance) + cv2(load) (fmoe.gates.NoisyGate).  ``logits2`` [T, 2E] =
+    [clean | raw] carries the gradient.  Backward: ONE pass (smoe_noisy_gate_bwd); without the loss in the objective (daux None) its
+    terms are left out."""
+
+    @staticmethod
+    def forward(ctx, logits2, eps, idx, score, keep, nxt, aux, coef_imp, coef_load, training):
+        ctx.training, ctx.has_eps = training, eps is not None
+        ctx.save_for_backward(logits2, idx, keep, nxt, coef_imp, coef_load, *((eps,) if eps is not None else ()))
+        ctx.set_materialize_grads(False)     # no aux loss in the objective: daux is None, not a zero tensor
+        return score.view_as(score), aux.view_as(aux)
+
+    @staticmethod
+    def backward(ctx, dscore, daux):
+        logits2, idx, keep, nxt, coef_imp, coef_load = ctx.saved_tensors[:6]
+        eps = ctx.saved_tensors[6] if ctx.has_eps else None
+        if dscore is None and daux is None:
+            return (None,) * 10
+        ds = dscore.to(torch.float32).contiguous() if dscore is not None else None
+        scale = daux.reshape(1).to(torch.float32) if daux is not None else None      # multiplied onto the coefficients inside the kernel
+        return (ops.noisy_gate_bwd(logits2, eps, idx, keep, nxt, ds, coef_imp, coef_load, scale, ctx.training),) + (None,) * 9
+
+
 def _zero_row_routing(mod):
     """(int64 [k] (device): the experts an all-zero row is routed to (top-k of the gate bias; ties -> lowest id), from the HIP
     router itself; the group -> expert map i32 [E + k]; the zero groups' ids int64 [1, k]), cached per version of the gate parameters."""
@@ -359,21 +383,42 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
     groups' weight gradients are rank-1 (_GroupFFN.backward).
     ``slots`` (dict with "tab": ep._SlotTable, "agreed": rows the table was agreed for): the plan in the slot layout of the static
     expert exchange (smoe_dispatch_plan_slots: pos has tab.rows entries, S is the send buffer); "counts" / "raw" come back in it."""
-    from .fmoe import GShardGate, SwitchGate
+    from .fmoe import GShardGate, NoisyGate, SwitchGate
 
     g = mod.gate
     k = mod.top_k
     T = x.shape[0]
     is_switch = isinstance(g, SwitchGate)
     is_gshard = isinstance(g, GShardGate)
+    is_noisy = isinstance(g, NoisyGate)
     noise = g.make_noise(T, x.device) if is_switch else None
-    gw = g.gate.weight.detach().float().contiguous()
-    gb = g.gate.bias.detach().float() if g.gate.bias is not None else None
-    need_grad = is_switch or k > 1
+    score_t = None
+    if is_noisy:
+        # the gate "linear" is the [2E, d] stack [w_gate^T ; w_noise^T], built differentiably from the two parameters: ONE router call
+        # yields clean and raw logits, and its gradients go back through the same nodes as any gate's
+        gate_w, gate_b = g.weight2(), None
+        gw, gb = gate_w.detach(), None
+        eps = g.make_noise(T, x.device) if g.training else None              # (eval: sigma = 0)
+        if not ops.noisy_gate_supported(g.tot_expert, k):                      # outside the kernels' range: the torch composition
+            idx, score_t = g(x.float(), eps)
+    else:
+        gate_w, gate_b = g.gate.weight, g.gate.bias
+        gw = gate_w.detach().float().contiguous()
+        gb = gate_b.detach().float() if gate_b is not None else None
+    need_grad = is_switch or k > 1 or is_noisy
     g_map, zero_groups = None, 0
     with torch.no_grad():
-        idx, score_c, logits_r, probs_r = ops.router_topk(x.detach(), gw, gb, k, g.kind, noise, want_logits=need_grad,
-                                                          want_probs=is_switch)
+        if score_t is not None:
+            score_c, logits_r = score_t.detach().float().contiguous(), None
+        elif is_noisy:
+            # (the router's own top-1 over the 2E columns is discarded: the decision is taken on the f32 noisy values)
+            _, _, logits_r, probs_r = ops.router_topk(x.detach(), gw, None, 1, ops.GATE_NAIVE, None, want_logits=True)
+            nz = ops.noisy_gate_fwd(logits_r, eps, k, g.training)
+            idx, score_c = nz["idx"], nz["score"]
+            g.last_noise = (eps, nz["imp"], nz["load"])
+        else:
+            idx, score_c, logits_r, probs_r = ops.router_topk(x.detach(), gw, gb, k, g.kind, noise, want_logits=need_grad,
+                                                              want_probs=is_switch)
         cap = g.capacity(T)
         E = g.tot_expert
         plan_idx, plan_cap = idx, cap
@@ -390,7 +435,8 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
                 inv_pos = torch.full((T * k,), -1, dtype=torch.int64, device=x.device)
                 inv_pos[: agreed * k].copy_(inv_h)
             slots["counts"], slots["raw"] = counts, raw
-        elif zero_rows is not None and not is_switch and not is_gshard and cap < 0 and E + k <= 63:
+        elif zero_rows is not None and not is_switch and not is_gshard and not is_noisy and cap < 0 and E + k <= 63:
+            # (nor for a NoisyGate: with noise, masked rows do not route alike)
             # (not for a GShardGate without a capacity: its plan runs over the pruned ids -- random routing still drops entries)
             _idx0, g_map, zero_ids = _zero_row_routing(mod)                                # (cached per gate-parameter version)
             idx_plan = torch.where(zero_rows.reshape(T, 1), zero_ids, idx)
@@ -400,14 +446,20 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
             counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(plan_idx, E, plan_cap)
     mod.last_plan = (idx, score_c, counts, offsets, pos, inv_pos)
     S = None
-    if need_grad:  # tiny [T,E] work -- the routing itself stays the HIP router's
+    if score_t is not None:
+        score = score_t.float()
+    elif need_grad:  # tiny [T,E] work -- the routing itself stays the HIP router's
         fused = (scatter_cd is not None and x.is_cuda and x.shape[1] % 4 == 0 and x.dtype in ops._DT
-                 and g.gate.weight.dtype == torch.float32)
+                 and gate_w.dtype == torch.float32)
         if fused:
-            logits, S = _GateScatter.apply(x, g.gate.weight, g.gate.bias, logits_r, pos, inv_pos, k, scatter_cd)
+            logits, S = _GateScatter.apply(x, gate_w, gate_b, logits_r, pos, inv_pos, k, scatter_cd)
         else:
-            logits = _GateLogits.apply(x, g.gate.weight, g.gate.bias, logits_r)
-        if is_switch:   # probs_r = softmax(logits + noise) and score_c = probs_r[idx] are the router's own
+            logits = _GateLogits.apply(x, gate_w, gate_b, logits_r)
+        if is_noisy:    # score and loss are smoe_noisy_gate_fwd's own; one node carries both back to the [T, 2E] logits
+            score, aux = _NoisyScoreAux.apply(logits, eps, idx, score_c, nz["keep"], nz["next"], nz["aux"], nz["coef_imp"],
+                                              nz["coef_load"], g.training)
+            g.set_loss(aux)
+        elif is_switch:   # probs_r = softmax(logits + noise) and score_c = probs_r[idx] are the router's own
             score, aux = _SwitchScoreAux.apply(logits, probs_r, score_c, idx, counts, g.tot_expert)
             g.set_loss(aux)
         elif is_gshard:  # score_c = softmax over the two chosen logits is the router's own; aux from the logits and the first choices

@@ -768,7 +768,7 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
     ONE pass) the routing is taken as given: ``idx`` / ``score`` [T, k], ``idx_plan`` (= idx, -1 for the tokens the skip gate
     masked: they are simply not sent), ``src`` = the 16-bit operand image the send buffers are gathered from."""
     from . import ops
-    from .fmoe import GShardGate, SwitchGate
+    from .fmoe import GShardGate, NoisyGate, SwitchGate
 
     g = mod.gate
     W, E_local, k, d = mod.world_size, mod.num_expert, mod.top_k, mod.d_model
@@ -795,6 +795,10 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
         score = torch.empty((0, k), dtype=torch.float32, device=x.device)
         probs = torch.empty((0, g.tot_expert), dtype=torch.float32, device=x.device)
         src = torch.empty((0, d), dtype=cd, device=x.device) if norm is not None else x
+    elif isinstance(g, NoisyGate) and g.training:
+        # a no-grad forward of a module left in training mode routes with noise (the fused LayerNorm pass is not offered to it)
+        assert norm is None, "ep_forward_steps: a NoisyGate in training mode takes the unfused sequence"
+        (idx, score), probs = g.route_noisy(x), None
     elif norm is not None:
         xn16, _, idx, score, _, probs = ops.ln_router_topk(
             x, norm.weight.detach().float(), norm.bias.detach().float() if norm.bias is not None else None, norm.eps,
@@ -804,6 +808,8 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
         idx, score, _, probs = ops.router_topk(x, gw, gb, k, g.kind, noise, want_probs=isinstance(g, SwitchGate))
     if plan_idx is None:
         plan_idx = idx
+    if isinstance(g, NoisyGate):
+        g.set_loss(None)
     if isinstance(g, GShardGate):
         # capacity (per source rank, on this rank's T rows) + random routing on the gate's own kernels: every plan below runs over
         # what is left, without a capacity of its own.  `cap` keeps deciding what a capacity gate decides (one chunk, static exchange).

@@ -193,6 +193,122 @@ class GShardGate(NaiveGate):
         return idx_out, top1
 
 
+class _GateImage:
+    """What the naive paths read as ``gate.gate`` of a NoisyGate: ``weight`` = the [E, d] f32 image of ``w_gate`` (no gradient), no bias."""
+    __slots__ = ("weight", "bias")
+
+    def __init__(self, weight):
+        self.weight, self.bias = weight, None
+
+
+class NoisyGate(nn.Module):
+    """Noisy top-k gate with the importance + load balance loss and no capacity (fmoe.gates.NoisyGate, Shazeer et al.; the rule is
+    restated in INTEGRATION.md).  Parameters ``w_gate`` / ``w_noise`` [d_model, E], no bias.  In training the router runs over the
+    [2E, d] image [w_gate^T ; w_noise^T] and the gate's own arithmetic runs behind it on smoe_noisy_gate_fwd / _bwd; in eval
+    (sigma = 0) the gate IS a bias-free NaiveGate over ``w_gate.T``: ``gate.gate`` hands every naive path that [E, d] image (cached
+    per parameter version; not a sub-module, so the state dict holds ``w_gate`` and ``w_noise`` and nothing else).
+    Calling the module (``gate(x)`` -> (idx, score)) is the differentiable torch composition of the rule: CPU tensors, and the
+    configurations the kernels do not take."""
+
+    kind = ops.GATE_NAIVE
+
+    def __init__(self, d_model: int, num_expert: int, world_size: int, top_k: int = 2):
+        super().__init__()
+        self.top_k = top_k
+        self.num_expert, self.world_size = num_expert, world_size
+        self.tot_expert = num_expert * world_size
+        if not 1 <= top_k < self.tot_expert:
+            # (upstream falls back to a count-based, non-differentiable load at top_k >= E: refused instead)
+            raise ValueError(f"NoisyGate: top_k={top_k} must be in [1, E) for E={self.tot_expert} experts (the load reads the "
+                             f"(k+1)-th value)")
+        self.w_gate = nn.Parameter(torch.empty(d_model, self.tot_expert))
+        self.w_noise = nn.Parameter(torch.empty(d_model, self.tot_expert))
+        self.noise_epsilon = 1e-2
+        self.loss = None
+        self.last_noise = None   # (eps, imp, load) of the latest training forward, for inspection
+        self._images = StreamCache()
+        self.register_load_state_dict_post_hook(lambda mod, _keys: mod._images.invalidate())
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.w_gate, a=math.sqrt(5))
+        nn.init.kaiming_uniform_(self.w_noise, a=math.sqrt(5))
+
+    def capacity(self, n_tokens: int) -> int:
+        return -1
+
+    def set_loss(self, loss):
+        self.loss = loss
+
+    def get_loss(self, clear: bool = True):
+        loss = self.loss
+        if clear:
+            self.loss = None
+        return loss
+
+    def make_noise(self, T: int, device) -> torch.Tensor:
+        return torch.randn(T, self.tot_expert, device=device)
+
+    @property
+    def gate(self) -> _GateImage:
+        w = self.w_gate
+        return _GateImage(self._images.get(("t", w.device), param_version(w), lambda: w.detach().t().float().contiguous()))
+
+    def weight2(self) -> torch.Tensor:
+        """[2E, d] = [w_gate^T ; w_noise^T], differentiable: the operand of the one router call that yields clean and raw logits."""
+        return torch.cat((self.w_gate.t(), self.w_noise.t()), 0).float()
+
+    def image2(self) -> torch.Tensor:
+        """``weight2()`` without a gradient, cached per version of the two parameters."""
+        ver = (param_version(self.w_gate), param_version(self.w_noise))
+        return self._images.get(("2", self.w_gate.device), ver, lambda: self.weight2().detach().contiguous())
+
+    def route_noisy(self, x: torch.Tensor):
+        """(idx, score) of a no-grad forward of a gate left in training mode: router over the [2E, d] image (its own top-1 is
+        discarded), then smoe_noisy_gate_fwd with a fresh draw.  No loss."""
+        T, E, k = x.shape[0], self.tot_expert, self.top_k
+        self.set_loss(None)
+        with torch.no_grad():
+            if not ops.noisy_gate_supported(E, k):
+                return self.forward(x.float())
+            _, _, logits2, _ = ops.router_topk(x, self.image2(), None, 1, ops.GATE_NAIVE, None, want_logits=True)
+            eps = self.make_noise(T, x.device)
+            r = ops.noisy_gate_fwd(logits2, eps, k, True)
+            self.last_noise = (eps, r["imp"], r["load"])
+        return r["idx"], r["score"]
+
+    @staticmethod
+    def cv2(v: torch.Tensor) -> torch.Tensor:
+        return v.var(unbiased=True) / (v.mean() ** 2 + 1e-10)
+
+    def forward(self, inp: torch.Tensor, eps: Optional[torch.Tensor] = None):
+        """(idx int64 [T, k], score [T, k]) by the rule as differentiable torch ops; sets the loss (None without grad)."""
+        E, k = self.tot_expert, self.top_k
+        x = inp.reshape(-1, inp.shape[-1])
+        clean = x @ self.w_gate.to(x.dtype)
+        if self.training:
+            sigma = torch.nn.functional.softplus(x @ self.w_noise.to(x.dtype)) + self.noise_epsilon
+            if eps is None:
+                eps = self.make_noise(x.shape[0], x.device)
+            noisy = clean + eps.to(x.dtype) * sigma
+        else:
+            noisy = clean
+        val, order = torch.sort(noisy, dim=1, descending=True, stable=True)      # (stable: ties -> lowest expert id)
+        idx, v = order[:, :k], val[:, :k + 1]
+        score = torch.softmax(v[:, :k], dim=-1)
+        if not (torch.is_grad_enabled() and (x.requires_grad or self.w_gate.requires_grad or self.w_noise.requires_grad)):
+            self.set_loss(None)
+            return idx, score
+        imp = torch.zeros(E, dtype=score.dtype, device=x.device).scatter_add(0, idx.reshape(-1), score.reshape(-1))
+        aux = self.cv2(imp)
+        if self.training:
+            thr = torch.where(noisy > v[:, k:k + 1], v[:, k:k + 1], v[:, k - 1:k])
+            load = (0.5 * (1.0 + torch.erf((clean - thr) / sigma * (1.0 / math.sqrt(2.0))))).sum(0)
+            aux = aux + self.cv2(load)
+        self.set_loss(aux)
+        return idx, score
+
+
 class _Expert(nn.Module):
     """fmoe.transformer._Expert: htoh4 -> activation -> h4toh over expert-sorted rows.
 
@@ -267,7 +383,7 @@ class FMoETransformerMLP(nn.Module):
 
     forward(x[..., d]) -> same shape:  router -> dispatch plan -> token scatter -> grouped GEMM (+bias,
     +GELU) -> grouped GEMM (+bias) -> gather/combine, all HIP kernels.
-    Keyword-only extensions with reference defaults: ``gate`` ("naive" | "switch" | "gshard" | a gate class),
+    Keyword-only extensions with reference defaults: ``gate`` ("naive" | "switch" | "gshard" | "noisy" | a gate class),
     ``capacity_factor``, ``world_size`` / ``moe_group`` (expert parallel), ``compute_dtype``.
     """
 
@@ -290,6 +406,8 @@ class FMoETransformerMLP(nn.Module):
             elif gate == "gshard":
                 cap = capacity_factor if capacity_factor is not None else (1.2, 2.4)
                 self.gate = GShardGate(d_model, num_expert, world_size, top_k, capacity=cap)
+            elif gate == "noisy":
+                self.gate = NoisyGate(d_model, num_expert, world_size, top_k)
             else:
                 raise ValueError(f"unknown gate {gate!r}")
         else:
@@ -370,7 +488,8 @@ class FMoETransformerMLP(nn.Module):
               and self.gemm_variant in (4, 9) and self.d_model % 64 == 0
               and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())
                                                     or any(p.requires_grad for p in norm.parameters())))
-              and ops.ln_router_supported(self.d_model, g.tot_expert, g.top_k))
+              and ops.ln_router_supported(self.d_model, g.tot_expert, g.top_k)
+              and not (isinstance(g, NoisyGate) and g.training))    # (noise: the unfused sequence, _route / ep_forward_steps)
         if not ok:
             return self.forward_add(norm(x), x)
         if self.ep_active():
@@ -399,6 +518,8 @@ class FMoETransformerMLP(nn.Module):
         # the router pass also counts for the plan (count_by_gate folded in) -- over all rows: of no use to a plan over some
         # (not for a GShardGate: its plan runs over the pruned ids, which the router has not seen)
         is_gshard = isinstance(g, GShardGate)
+        if isinstance(g, NoisyGate):
+            g.set_loss(None)      # (eval: sigma = 0, the gate is the bias-free NaiveGate over w_gate.T from here on)
         hist = ops.chunk_hist(T, d, g.tot_expert, k, x2.device) if sub is None and not is_gshard else None
         xn16, _, idx, score, _, probs = ops.ln_router_topk(
             x2, norm.weight.detach().float(), norm.bias.detach().float() if norm.bias is not None else None, norm.eps,
@@ -576,6 +697,12 @@ class FMoETransformerMLP(nn.Module):
     def _route(self, x: torch.Tensor):
         g = self.gate
         T = x.shape[0]
+        if isinstance(g, NoisyGate):
+            g.set_loss(None)
+            if g.training:        # a no-grad forward of a module left in training mode routes with noise
+                idx, score = g.route_noisy(x)
+                counts, offsets, pos, inv_pos, _ = ops.dispatch_plan(idx, g.tot_expert, -1)
+                return idx, score, None, counts, offsets, pos, inv_pos, None
         noise = g.make_noise(T, x.device) if isinstance(g, SwitchGate) else None
         want_probs = isinstance(g, SwitchGate)
         gw = g.gate.weight.detach()

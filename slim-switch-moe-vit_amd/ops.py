@@ -1194,6 +1194,88 @@ def gshard_gate_bwd(logits: torch.Tensor, idx: torch.Tensor, idx_out: torch.Tens
     return out
 
 
+NOISY_MAX_E, NOISY_MAX_K = 32, 4     # the range of smoe_noisy_gate_fwd / _bwd (2 <= E, 1 <= k < E)
+
+
+def noisy_gate_supported(E: int, k: int) -> bool:
+    return 2 <= E <= NOISY_MAX_E and 1 <= k <= NOISY_MAX_K and k < E
+
+
+def _noisy_logits2(logits2: torch.Tensor, eps: Optional[torch.Tensor]):
+    """``logits2`` is a contiguous f32 [T, 2E] tensor ([clean | raw]) and ``eps`` f32 [T, E] or None; returns (T, E)."""
+    _chk(logits2, "logits2", torch.float32, 2, align=4)
+    T, E2 = logits2.shape
+    if E2 % 2:
+        raise RuntimeError(f"logits2: expected [T, 2E] (clean | raw), got {tuple(logits2.shape)}")
+    if eps is not None:
+        _chk(eps, "eps", torch.float32, 2, align=4)
+        if tuple(eps.shape) != (T, E2 // 2):
+            raise RuntimeError(f"eps: expected {(T, E2 // 2)}, got {tuple(eps.shape)}")
+    return T, E2 // 2
+
+
+def noisy_gate_fwd(logits2: torch.Tensor, eps: Optional[torch.Tensor], k: int, training: bool = True):
+    """The noisy top-k gate's forward on the router's ``logits2`` [T, 2E] = [clean | raw] (smoe_noisy_gate_fwd; rule in INTEGRATION.md).
+    Returns a dict: ``idx`` i64 [T, k], ``score`` f32 [T, k] (softmax over the k largest noisy values), ``keep`` f64 [T, 2] =
+    (v_k, v_{k+1}) and ``next`` i32 [T] = the (k+1)-th expert (what noisy_gate_bwd wants kept), ``imp`` / ``load`` f32 [E], ``aux`` f32 []
+    = cv2(imp) + cv2(load), ``coef_imp`` / ``coef_load`` f32 [E] = d aux / d imp, d aux / d load.  ``eps`` None = zero noise;
+    ``training`` False = sigma 0 (no noise, no load term).  Two launches, bit-reproducible."""
+    T, E = _noisy_logits2(logits2, eps)
+    dev = logits2.device
+    lib = _lib.load()
+    ws_bytes = lib.smoe_noisy_gate_workspace_bytes(T, E)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    idx = torch.empty((T, int(k)), dtype=torch.int64, device=dev)
+    score = torch.empty((T, int(k)), dtype=torch.float32, device=dev)
+    keep = torch.empty((T, 2), dtype=torch.float64, device=dev)
+    nxt = torch.empty((T,), dtype=torch.int32, device=dev)
+    vec = torch.empty(4 * E + 1, dtype=torch.float32, device=dev)       # imp | load | coef_imp | coef_load | aux
+    base = vec.data_ptr()
+    with _timed("noisy_gate_fwd", {"bytes": T * (12 * E + 12 * int(k) + 20)}, logits2):
+        rc = lib.smoe_noisy_gate_fwd(_ptr(logits2), _ptr(eps), T, E, int(k), 1 if training else 0, _ptr(idx), _ptr(score), _ptr(keep),
+                                     _ptr(nxt), base, base + 4 * E, base + 16 * E, base + 8 * E, base + 12 * E, _ptr(ws), ws_bytes,
+                                     _stream(logits2))
+    _lib.check(rc, "smoe_noisy_gate_fwd")
+    return dict(idx=idx, score=score, keep=keep, next=nxt, imp=vec[:E], load=vec[E:2 * E], coef_imp=vec[2 * E:3 * E],
+                coef_load=vec[3 * E:4 * E], aux=vec[4 * E])
+
+
+def noisy_gate_bwd(logits2: torch.Tensor, eps: Optional[torch.Tensor], idx: torch.Tensor, keep: torch.Tensor, nxt: torch.Tensor,
+                   dscore: Optional[torch.Tensor], coef_imp: Optional[torch.Tensor],
+                   coef_load: Optional[torch.Tensor], coef_scale: Optional[torch.Tensor] = None, training: bool = True) -> torch.Tensor:
+    """dlogits2 [T, 2E] of the noisy gate's score (``dscore`` [T, k] or None) and loss (``coef_imp`` / ``coef_load`` from noisy_gate_fwd
+    times ``coef_scale``, a one-element f32 device tensor = d loss / d aux; None = the loss is not in the objective) in one pass."""
+    T, E = _noisy_logits2(logits2, eps)
+    _chk(idx, "idx", torch.int64, 2, align=8)
+    k = idx.shape[1]
+    if idx.shape[0] != T:
+        raise RuntimeError(f"idx: expected {T} rows, got {idx.shape[0]}")
+    if dscore is not None:
+        _chk(dscore, "dscore", torch.float32, 2, align=4)
+        if tuple(dscore.shape) != (T, k):
+            raise RuntimeError(f"dscore: expected {(T, k)}, got {tuple(dscore.shape)}")
+    _chk(keep, "keep", torch.float64, 2, align=8)
+    _chk(nxt, "next", torch.int32, 1, align=4)
+    if tuple(keep.shape) != (T, 2) or nxt.numel() != T:
+        raise RuntimeError("noisy_gate_bwd: keep is [T, 2] and next [T], as noisy_gate_fwd wrote them")
+    if coef_scale is not None:
+        _chk(coef_scale, "coef_scale", torch.float32, align=4)
+        if coef_imp is None or coef_load is None or coef_scale.numel() != 1:
+            raise RuntimeError("noisy_gate_bwd: coef_scale is one element and needs both coefficient vectors")
+    for t, name in ((coef_imp, "coef_imp"), (coef_load, "coef_load")):
+        if t is not None:
+            _chk(t, name, torch.float32, 1, align=4)
+            if t.numel() != E:
+                raise RuntimeError(f"noisy_gate_bwd: {name} holds one coefficient per expert")
+    out = torch.empty_like(logits2)
+    with _timed("noisy_gate_bwd", {"bytes": T * (20 * E + 12 * k + 20)}, logits2):
+        rc = _lib.load().smoe_noisy_gate_bwd(_ptr(logits2), _ptr(eps), _ptr(idx), _ptr(keep), _ptr(nxt), _ptr(dscore),
+                                             _ptr(coef_imp), _ptr(coef_load), _ptr(coef_scale), T, E, k, 1 if training else 0, _ptr(out),
+                                             _stream(logits2))
+    _lib.check(rc, "smoe_noisy_gate_bwd")
+    return out
+
+
 def pad_offsets(offsets: torch.Tensor) -> torch.Tensor:
     _chk(offsets, "offsets", torch.int32, 1)
     out = torch.empty_like(offsets)
