@@ -218,6 +218,40 @@ int smoe_attention_bwd_supported(int N, int head_dim);
 int smoe_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int B, int N,
                        int H, int head_dim, float scale, void* stream);
 
+/* ---- skip-aware attention half (eval; csrc/attention_skip.hip; additive to ABI 29) ------------------------------------------
+ * With a hard dense_gate a bypassed token's operand row is exactly zero, so its q / k / v are the rounded qkv bias: per image with
+ * n entering and m = N - n bypassed tokens the attention half needs n + 1 rows (n when m == 0) -- the m equal keys are one key
+ * whose probability counts m times, the m equal queries one query whose projection row is added to every bypassed residual row.
+ * Every entry point: no allocation, no synchronisation, no float atomics, the same bits on every call, capturable.
+ *
+ * smoe_skip_plan: mask f32 [B*N, 2] as smoe_gate_ln_router writes it (channel 0 > 0.5 = bypassed) -> all on the device,
+ *   row_start / len / mult  i32 [B]: image b owns the compact rows [row_start[b], row_start[b] + len[b]), len = n_b + (m_b > 0),
+ *                           mult = m_b; row_start is the running sum of len
+ *   gather   i64 [B*N]      compact row -> token row: the entering tokens of image 0 in token order, then image 0's FIRST bypassed
+ *                           token as its representative (if m_0 > 0), then image 1, ...; R = sum len <= B*N rows are in use
+ *   row_map  i64 [B*N]      compact row -> output row of the projection: the token row, or B*N + b for image b's representative
+ *   offsets  i32 [2]        {0, R}: the one row group of both GEMMs
+ *   rep_row  i32 [B*N]      per token: B*N + b for a bypassed token of image b, -1 for an entering one
+ *   entries of gather / row_map at and past R belong to no row group; they are set to 0 / B*N.
+ *   park (may be NULL): f32 [B, park_cols], zeroed -- the B rows behind the token matrix that hold the representatives' outputs
+ *   (the projection adds its `residual` row, which must be zero there).  B*N + B < 2^31.
+ * smoe_attention_fwd_varlen: smoe_attention_fwd's one-pass forward over the compact qkv [rows_cap, 3, H, 64] -> out [rows_cap, H*64]
+ *   (the same compact rows), one workgroup per (image, head); rows and key count of image b from row_start / len, and with
+ *   mult[b] > 0 the image's LAST key counts mult[b] times.  max_len (host-side bound on len, <= 256) picks the instantiation; an image
+ *   whose plan entry does not fit (len < 1, len > max_len rounded up to the instantiation, rows outside [0, rows_cap)) is left
+ *   unwritten.  flags: SMOE_VARLEN_WEIGHT_SCORE = log2(mult) is added to the last key's scaled score instead of multiplying its
+ *   probability (default: the probability, exact for an integer); SMOE_VARLEN_NO_TIERS = every image walks the key-tile count of
+ *   max_len (default: an image takes the smallest of 4 / 8 / 13 / 16 tiles that holds its len).  f16 / bf16, head dim 64.
+ * smoe_skip_expand: out[t, :] = xn32[t, :] + out[rep_row[t], :] for every t < T with rep_row[t] >= 0; other rows untouched.  xn32 may
+ *   be out itself.  f32, d % 4 == 0, out_rows = rows allocated in out (rep_row values at or past it are ignored).           */
+enum { SMOE_VARLEN_WEIGHT_SCORE = 1, SMOE_VARLEN_NO_TIERS = 2 };
+int smoe_skip_plan(const float* mask, int B, int N, int32_t* row_start, int32_t* len, int32_t* mult, int64_t* gather,
+                   int64_t* row_map, int32_t* offsets, int32_t* rep_row, float* park, int park_cols, void* stream);
+int smoe_attention_fwd_varlen(const void* qkv, void* out, int dtype, const int32_t* row_start, const int32_t* len,
+                              const int32_t* mult, int B, int max_len, int64_t rows_cap, int H, int head_dim, float scale,
+                              int flags, void* stream);
+int smoe_skip_expand(const float* xn32, const int32_t* rep_row, float* out, int64_t T, int d, int64_t out_rows, void* stream);
+
 /* ---- dispatch plan --------------------------------------------------------------------------------
  * Replaces fmoe_cuda.expert_count + cumsum + assign_pos (+ limit_by_capacity /
  * prune_gate_by_capacity) = fmoe count_by_gate / prepare_forward.

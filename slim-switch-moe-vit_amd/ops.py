@@ -319,6 +319,83 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
     return dqkv
 
 
+# ---- skip-aware attention half (eval): plan -> gathered qkv GEMM -> varlen attention -> projection with a row map -> expand ----
+VARLEN_WEIGHT_SCORE, VARLEN_NO_TIERS = 1, 2   # flags of smoe_attention_fwd_varlen (include/slimmoe.h)
+VARLEN_MAX_LEN = 256
+
+
+def skip_attention_supported(N: int, head_dim: int) -> bool:
+    """Shapes smoe_attention_fwd_varlen covers: the one-pass form (N <= 256), head dim 64."""
+    return 1 <= N <= VARLEN_MAX_LEN and head_dim == 64
+
+
+def skip_plan(mask: torch.Tensor, B: int, N: int, park: Optional[torch.Tensor] = None) -> dict:
+    """The gate's mask (f32 [B*N, 2], channel 0 = bypassed) -> the device-side plan of the skip-aware attention half: per-image
+    ``row_start`` / ``len`` / ``mult`` (i32 [B]), ``gather`` and ``row_map`` (i64 [B*N]), ``offsets`` (i32 [2] = [0, R]) and ``rep_row``
+    (i32 [B*N]).  ``park`` (f32 [B, d]): the representatives' output rows behind the token matrix, zeroed by the same call.  The host
+    never learns R."""
+    _chk(mask, "mask", torch.float32, align=4)
+    T = B * N
+    if mask.numel() != T * 2 or B < 1 or N < 1:
+        raise RuntimeError(f"mask: expected [B*N, 2] with B={B}, N={N}, got {tuple(mask.shape)}")
+    cols = 0
+    if park is not None:
+        _chk(park, "park", torch.float32, 2, align=4)
+        if park.shape[0] != B:
+            raise RuntimeError(f"park: expected [{B}, d], got {tuple(park.shape)}")
+        cols = park.shape[1]
+    dev = mask.device
+    i32 = torch.empty(4 + 3 * B + T, dtype=torch.int32, device=dev)      # one allocation for the small tables (offsets 16-byte aligned)
+    offsets, row_start, length, mult, rep_row = i32[:2], i32[4:4 + B], i32[4 + B:4 + 2 * B], i32[4 + 2 * B:4 + 3 * B], i32[4 + 3 * B:]
+    i64 = torch.empty(2 * T, dtype=torch.int64, device=dev)
+    gather, row_map = i64[:T], i64[T:]
+    with _timed("skip_plan", {"bytes": T * (8 + 16 + 4)}, mask):
+        rc = _lib.load().smoe_skip_plan(_ptr(mask), B, N, _ptr(row_start), _ptr(length), _ptr(mult), _ptr(gather), _ptr(row_map),
+                                        _ptr(offsets), _ptr(rep_row), _ptr(park), cols, _stream(mask))
+    _lib.check(rc, "smoe_skip_plan")
+    return {"row_start": row_start, "len": length, "mult": mult, "gather": gather, "row_map": row_map, "offsets": offsets,
+            "rep_row": rep_row, "B": B, "N": N}
+
+
+def attention_varlen(qkv: torch.Tensor, row_start: torch.Tensor, length: torch.Tensor, mult: torch.Tensor, max_len: int, H: int,
+                     head_dim: int, scale: float, flags: int = 0) -> torch.Tensor:
+    """softmax(q k^T * scale) v over the compact qkv [rows, 3*H*head_dim] (16 bit): image b owns the rows [row_start[b], row_start[b]
+    + len[b]) and, with mult[b] > 0, its last key counts mult[b] times -> [rows, H*head_dim], the same compact rows (rows no image
+    owns are not written).  ``max_len``: host-side bound on every len (<= 256)."""
+    _chk(qkv, "qkv", ndim=2)
+    if qkv.dtype not in (torch.float16, torch.bfloat16) or qkv.shape[1] != 3 * H * head_dim:
+        raise RuntimeError("qkv: expected a 16-bit [rows, 3*H*hd] tensor")
+    if not skip_attention_supported(max_len, head_dim):
+        raise RuntimeError(f"attention_varlen: max_len={max_len}, head_dim={head_dim} outside the kernel's reach (<= 256, 64)")
+    B = row_start.numel()
+    for t, nm in ((row_start, "row_start"), (length, "len"), (mult, "mult")):
+        _chk(t, nm, torch.int32, 1, align=4)
+        if t.numel() != B:
+            raise RuntimeError(f"{nm}: expected {B} entries")
+    rows = qkv.shape[0]
+    out = torch.empty((rows, H * head_dim), dtype=qkv.dtype, device=qkv.device)
+    with _timed("attention_varlen", {"flops": 4.0 * B * H * max_len * max_len * head_dim}, qkv):
+        rc = _lib.load().smoe_attention_fwd_varlen(_ptr(qkv), _ptr(out), dtype_code(qkv.dtype), _ptr(row_start), _ptr(length),
+                                                   _ptr(mult), B, max_len, rows, H, head_dim, float(scale), int(flags), _stream(qkv))
+    _lib.check(rc, "smoe_attention_fwd_varlen")
+    return out
+
+
+def skip_expand(xn32: torch.Tensor, rep_row: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """``out[t] = xn32[t] + out[rep_row[t]]`` for every token t with ``rep_row[t] >= 0`` (the bypassed ones); other rows of ``out``
+    are untouched.  ``xn32`` [T, d] f32 may be the first T rows of ``out`` [>= T, d] itself."""
+    _chk(xn32, "xn32", torch.float32, 2)
+    _chk(out, "out", torch.float32, 2)
+    _chk(rep_row, "rep_row", torch.int32, 1, align=4)
+    T, d = xn32.shape
+    if out.shape[1] != d or out.shape[0] < T or rep_row.numel() != T or d % 4:
+        raise RuntimeError("skip_expand: expected xn32 [T, d], out [>= T, d], rep_row [T], d % 4 == 0")
+    with _timed("skip_expand", {"bytes": 0}, out):
+        rc = _lib.load().smoe_skip_expand(_ptr(xn32), _ptr(rep_row), _ptr(out), T, d, out.shape[0], _stream(out))
+    _lib.check(rc, "smoe_skip_expand")
+    return out
+
+
 def ln_router_supported(d: int, E: int, k: int) -> bool:
     return bool(_lib.load().smoe_ln_router_supported(d, E, k))
 

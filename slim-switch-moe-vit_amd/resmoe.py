@@ -290,11 +290,22 @@ def _residual_block_fused(blk, x):
       attention half   norm1 + dense_gate in ONE pass over x (ops.gate_ln_router): the fp16 operand image of the
                        tokens that enter attention (zero rows for the bypassing ones) and the f32 residual image;
                        qkv GEMM -> attention kernel -> projection GEMM with `+ residual` in its store
+                       (with the block's skip_aware_attention: the three over the entering rows plus one bypassed row per image,
+                       _attention_half_skip -- the same function up to the order of the sums)
       MoE half         norm2 + moe_gate + router in ONE pass (FMoETransformerMLP.forward_norm_gate_add): bypassing tokens
                        are all-zero rows for the experts, so they are not dispatched at all -- what they would receive
                        (the per-layer constant of ops.zero_row_output) is added to their residual row by the same pass;
                        GEMM-1 gathers its rows from the fp16 image, GEMM-2 adds into the residual image in place.
     Preconditions: _fused_ok."""
+    if _skip_attention_ok(blk, x):
+        x, _ = _attention_half_skip(blk, x)
+    else:
+        x, _ = _attention_half_fused(blk, x)
+    return blk.mlp.forward_norm_gate_add(x, blk.norm2, blk.moe_gate)
+
+
+def _attention_half_fused(blk, x, want_mask: bool = False):
+    """The attention half of _residual_block_fused over all B*N rows -> (norm1(x) + attn(entering rows), the gate's mask | None)."""
     B, N, d = x.shape
     g = blk.dense_gate
     lin = g.head[1]
@@ -303,12 +314,36 @@ def _residual_block_fused(blk, x):
         g._total_tokens += B * N
     r = ops.gate_ln_router(x.reshape(B * N, d), lin.weight, lin.bias, g.active_threshold(),
                            ln=(n1.weight.detach(), n1.bias.detach() if n1.bias is not None else None, n1.eps),
-                           xn16_dtype=th.float16, want_xn32=True,
+                           xn16_dtype=th.float16, want_xn32=True, want_mask=want_mask,
                            skip_count=None if g.disable else g.skip_counter(x.device))
     res = r["xn32"].reshape(B, N, d)
     a, added = blk.attn(r["xn16"].reshape(B, N, d), residual=res)
-    x = a if added else a + res
-    return blk.mlp.forward_norm_gate_add(x, blk.norm2, blk.moe_gate)
+    return (a if added else a + res), r["mask"]
+
+
+def _skip_attention_ok(blk, x) -> bool:
+    """Whether the attention half takes the skip-aware path: the block's flag (VisionTransformer.skip_aware_attention hands it
+    down), an enabled gate, and a shape the varlen attention and the own dense GEMM cover -- all of it known to the host."""
+    return (getattr(blk, "skip_aware_attention", False) and not blk.dense_gate.disable
+            and blk.attn.skip_supported(x.shape[1], x.shape[2]))
+
+
+def _attention_half_skip(blk, x):
+    """The same half over the rows that need it (Attention.forward_skip16): per image the tokens the gate lets in and ONE bypassed
+    row.  The gate's pass is the one _attention_half_fused runs, with the mask stored as well; the counters move as they do there.
+    -> (out, mask).  Preconditions: _fused_ok and _skip_attention_ok."""
+    B, N, d = x.shape
+    T = B * N
+    g = blk.dense_gate
+    lin = g.head[1]
+    n1 = blk.norm1
+    g._total_tokens += T
+    res = th.empty((T + B, d), dtype=th.float32, device=x.device)   # the residual image + one parked output row per image
+    r = ops.gate_ln_router(x.reshape(T, d), lin.weight, lin.bias, g.active_threshold(),
+                           ln=(n1.weight.detach(), n1.bias.detach() if n1.bias is not None else None, n1.eps),
+                           xn16_dtype=th.float16, xn32_out=res[:T], want_mask=True, skip_count=g.skip_counter(x.device))
+    out, _ = blk.attn.forward_skip16(r["xn16"], res, r["mask"], B, N)
+    return out, r["mask"]
 
 
 def forward_residule_moe(self, x):

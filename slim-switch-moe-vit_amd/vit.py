@@ -328,6 +328,40 @@ class Attention(nn.Module):
             out = F.linear(o, hc.get(self.proj.weight), hc.get(self.proj.bias) if self.proj.bias is not None else None)
         return out.reshape(B, N, C), False
 
+    def skip_supported(self, N: int, C: int) -> bool:
+        """Whether ``forward_skip16`` covers this shape: the one-pass attention form (N <= 256), head dim 64, the own dense GEMM."""
+        from . import ops
+        return (DENSE_GEMM == "own" and C % self.num_heads == 0 and ops.skip_attention_supported(N, C // self.num_heads)
+                and self.qkv.weight.is_cuda and self.qkv.weight.dtype == torch.float32)
+
+    def forward_skip16(self, x16, res, mask, B: int, N: int):
+        """The attention half of a residual-MoE block in eval over the rows that need it (resmoe._residual_block_fused with
+        ``skip_aware_attention``).  ``x16`` [B*N, C] fp16: the gate's operand image, all-zero rows for the bypassed tokens; ``res``
+        [B*N + B, C] f32: the normed residual in its first B*N rows (the B rows behind them park the representatives' outputs);
+        ``mask`` [B*N, 2] f32: the hard gate's mask.
+
+        A bypassed token's q / k / v are the rounded qkv bias, so per image the n entering rows and ONE bypassed row are enough: the m
+        equal keys are one key counted m times, the m equal queries one query whose projection row is added to every bypassed
+        residual row.  plan -> qkv GEMM (gathered rows, device-side offsets) -> varlen attention -> projection GEMM (row map +
+        residual, in place) -> expand.  No host read: the row count stays on the device.  -> (out [B, N, C], True): the same function
+        as ``_forward_infer16`` with the residual up to the order of floating-point sums."""
+        from . import ops
+        T, C = B * N, x16.shape[1]
+        H = self.num_heads
+        hc = _half_cache(self)
+        plan = ops.skip_plan(mask, B, N, park=res[T:])
+        wq = hc.get(self.qkv.weight).reshape(3 * C, C)[None]
+        bq = hc.get_f32(self.qkv.bias)[None] if self.qkv.bias is not None else None
+        qkv = ops.grouped_gemm(x16, wq, bq, plan["offsets"], ops.EPI_NONE, torch.float16, a_gather=plan["gather"],
+                               variant=ops.DEFAULT_GEMM_VARIANT, prof_name="qkv_gemm_skip")
+        o = ops.attention_varlen(qkv, plan["row_start"], plan["len"], plan["mult"], N, H, C // H, self.scale)
+        wp = hc.get(self.proj.weight).reshape(C, C)[None]
+        bp = hc.get_f32(self.proj.bias)[None] if self.proj.bias is not None else None
+        ops.grouped_gemm(o, wp, bp, plan["offsets"], ops.EPI_NONE, torch.float32, row_map=plan["row_map"], residual=res, out=res,
+                         variant=ops.DEFAULT_GEMM_VARIANT, prof_name="attn_proj_gemm_skip")
+        ops.skip_expand(res[:T], plan["rep_row"], res)
+        return res[:T].reshape(B, N, C), True
+
     def _forward_train(self, x, residual, row_scale=None):
         """The training step's attention half on the library's kernels, forward AND backward (dense.py): fp16 rows from the
         HIP LayerNorm -> qkv GEMM -> attention -> projection GEMM (+ the f32 residual, and stochastic depth's per-row factor, in
@@ -380,6 +414,8 @@ class Block(nn.Module):
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+
+    skip_aware_attention = False   # what VisionTransformer.skip_aware_attention hands down (read by resmoe._residual_block_fused)
 
     def _norm1(self, x):
         """norm1 for the attention half; under fp16-autocast inference the LayerNorm writes fp16 directly (the cast
@@ -611,7 +647,16 @@ class VisionTransformer(nn.Module):
         x = self.pos_drop(x + self.pos_embed)
         return (x, None) if want_xn1 else x
 
+    # opt-in (True): in eval a residual-MoE block's attention half runs over the tokens its dense_gate lets in plus ONE bypassed row per
+    # image instead of all B*N rows (resmoe._residual_block_fused; N <= 256, head dim 64, the own dense GEMM, an enabled gate).  The
+    # same function as the default path up to the order of floating-point sums; no host read, graph-capturable.
+    skip_aware_attention = False
+
     def forward_features(self, x):
+        flag = bool(self.skip_aware_attention)
+        for blk in self.blocks:     # the blocks read their own attribute (a block may also be called on its own)
+            if getattr(blk, "skip_aware_attention", False) != flag:
+                blk.skip_aware_attention = flag
         n = self._ep_pipeline_depth(x)
         if self._ep_blocks():
             # the static exchange's buffers are agreed and sized per micro-batch (ep.static_slot_tokens): the modules must know how
