@@ -783,6 +783,39 @@ int smoe_bce_fwd(const void* logits, int dtype, const float* target, int binariz
 int smoe_bce_bwd(const void* logits, int dtype, const float* target, int binarize, int64_t B, int C, const float* g, void* dlogits,
                  void* stream);
 
+/* ---- SwitchableLayerNorm (models/layers.py:31-157, the rule of its forward at 105-151; the `router` of SwitchableVisionTransformer,
+ * models/vision_transformer.py:407 and 591) ---------------------------------------------------------------------------------------------
+ * x [T, d] f32; weights, biases, centroids [K, d] f32.  Per row: mean and biased variance over d, xhat = (x - mean) rsqrt(var + eps);
+ * the row's bucket b; y = xhat weights[b] + biases[b] (weights == NULL: y = xhat, biases must be NULL too; biases == NULL: no shift).
+ * The bucket is buckets_in[t] (int64 [T]) when that is given, else bucket_all (>= 0) for every row, else -- both unused, bucket_all ==
+ * -1 -- the SELECTED one: argmin_k sum_j (x_j - c_kj)^2 over the raw row, the first minimum, a NaN distance counting as the smallest
+ * and the first NaN winning (torch.argmin).  The distances are accumulated in double in this direct form, so the selection is the
+ * float64 evaluation's wherever the two smallest distances differ by more than float64's own error (upstream's f32 torch.cdist takes
+ * the expanded form and misassigns rows near a bisector).  K == 1 selects bucket 0 and never reads centroids (may be NULL); centroids
+ * are not read either when the buckets are given.
+ * smoe_switch_ln_supported : d % 4 == 0, 4 <= d <= 1024, 1 <= K <= 32.
+ * smoe_switch_ln_fwd : y f32 [T, d], buckets_out int64 [T] (the bucket used, also when it was given).  One launch, one wave per row,
+ *                    two-pass statistics in registers; x is not written.  No row statistics are kept: the backward recomputes them
+ *                    from x, as smoe_layernorm_bwd does.  A given bucket outside [0, K) reads nothing from the tables: its y row is NaN
+ *                    and buckets_out repeats the value.
+ * smoe_switch_ln_bwd : dy [T, d] f32 / f16 / bf16; dx f32 [T, d] = rstd (g - mean(g) - xhat mean(g xhat)), g = dy weights[b] (nothing
+ *                    flows through the selection; a bucket outside [0, K): a NaN row); dweights[k] = sum over the rows of bucket k of
+ *                    dy xhat, dbiases[k] = sum of dy, both f32 [K, d] (both NULL: not computed).  The sums are deterministic: partial
+ *                    tables per workgroup in the workspace, added in a fixed order -- the same bits run to run -- and the rows of an
+ *                    empty bucket are exact zeros.  centroids get no gradient.  Four launches (dx; column sums; two reduce stages).
+ * Non-finite inputs: nothing is masked.  A NaN in a row of x makes that row's y (and dx) NaN and every distance NaN, so the row selects
+ * bucket 0; no other row changes a bit.  A NaN centroid k draws every finite row to k (the smallest such k).  A NaN row of dy poisons
+ * its own dx row and the two gradient rows of its own bucket, nothing else.
+ * T >= 0 (T == 0: the forward returns at once; the backward writes zero gradients); rows are addressed in 64 bits.  x, y, dx and the
+ * tables 16-byte aligned.  Arguments are checked before any launch; no allocation, no host read, no atomics: both can be captured.  */
+int smoe_switch_ln_supported(int d, int K);
+int smoe_switch_ln_fwd(const float* x, const float* weights, const float* biases, const float* centroids, const int64_t* buckets_in,
+                       int bucket_all, float eps, int64_t T, int d, int K, float* y, int64_t* buckets_out, void* stream);
+size_t smoe_switch_ln_bwd_workspace_bytes(int64_t T, int d, int K);
+int smoe_switch_ln_bwd(const float* x, const void* dy, int dy_dtype, const float* weights, const int64_t* buckets, float eps,
+                       int64_t T, int d, int K, float* dx, float* dweights, float* dbiases, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- small helpers ------------------------------------------------------------------------------------
  * elementwise cast between dtypes (weight shadow copies; not on the per-step path)                  */
 int smoe_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);

@@ -1803,3 +1803,98 @@ def bce_bwd(logits: torch.Tensor, target: torch.Tensor, g: torch.Tensor, binariz
                                       _stream(logits))
     _lib.check(rc, "smoe_bce_bwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------- SwitchableLayerNorm
+SWITCH_LN_MAX_BUCKETS = 32
+
+
+def switch_ln_supported(d: int, K: int) -> bool:
+    """The reach of smoe_switch_ln_fwd / _bwd: d % 4 == 0, 4 <= d <= 1024 (LN_DIMS among them), 1 <= K <= 32 buckets."""
+    return bool(_lib.load().smoe_switch_ln_supported(int(d), int(K)))
+
+
+def _switch_ln_tables(x, weights, biases, centroids):
+    d = x.shape[-1]
+    K = None
+    for t, name in ((weights, "weights"), (biases, "biases"), (centroids, "centroids")):
+        if t is None:
+            continue
+        _chk(t, name, torch.float32, 2)
+        if t.shape[1] != d or t.device != x.device or (K is not None and t.shape[0] != K):
+            raise RuntimeError(f"switch_ln: {name} must be f32 [K, {d}] on x's device, got {tuple(t.shape)}")
+        K = t.shape[0]
+    return K
+
+
+def switch_ln(x: torch.Tensor, weights: Optional[torch.Tensor], biases: Optional[torch.Tensor], centroids: Optional[torch.Tensor],
+              eps: float, buckets=None, num_buckets: Optional[int] = None):
+    """SwitchableLayerNorm's rule (models/layers.py:105-151) in one launch (smoe_switch_ln_fwd): ``x`` f32 [..., d]; ``weights`` /
+    ``biases`` / ``centroids`` f32 [K, d] (weights and biases None: no affine); ``buckets``: None = selected per row (the exact argmin
+    of the squared distances to the centroids; K == 1 reads no centroids), an int = that bucket for every row, or an int64 tensor
+    of ``x.shape[:-1]``.  -> (y f32 like x, buckets int64 ``x.shape[:-1]``).  x is not modified."""
+    _chk(x, "x", torch.float32)
+    d = x.shape[-1]
+    T = x.numel() // d if d else 0
+    K = _switch_ln_tables(x, weights, biases, centroids)
+    if K is None:
+        K = num_buckets
+    if K is None:
+        raise RuntimeError("switch_ln: without tables the number of buckets must be given")
+    if biases is not None and weights is None:
+        raise RuntimeError("switch_ln: biases without weights")
+    if not switch_ln_supported(d, K):
+        raise RuntimeError(f"switch_ln: d={d}, K={K} outside the kernel's reach (d % 4 == 0, d <= 1024, K <= {SWITCH_LN_MAX_BUCKETS})")
+    b_in, b_all = None, -1
+    if isinstance(buckets, torch.Tensor):
+        _chk(buckets, "buckets", torch.int64, align=8)
+        if tuple(buckets.shape) != tuple(x.shape[:-1]) or buckets.device != x.device:
+            raise RuntimeError("switch_ln: buckets must be int64 of x.shape[:-1] on x's device")
+        b_in = buckets
+    elif buckets is not None:
+        b_all = int(buckets)
+        if not 0 <= b_all < K:
+            raise RuntimeError(f"switch_ln: bucket {b_all} outside [0, {K})")
+    elif K > 1 and centroids is None:
+        raise RuntimeError("switch_ln: centroids needed to select among K > 1 buckets")
+    y = torch.empty_like(x)
+    out_b = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device)
+    with _timed("switch_ln", {"bytes": T * d * 8}, x):
+        rc = _lib.load().smoe_switch_ln_fwd(_ptr(x), _ptr(weights), _ptr(biases), _ptr(centroids), _ptr(b_in), b_all, float(eps), T, d, K,
+                                            _ptr(y), _ptr(out_b), _stream(x))
+    _lib.check(rc, "smoe_switch_ln_fwd")
+    return y, out_b
+
+
+def switch_ln_bwd(x: torch.Tensor, dy: torch.Tensor, weights: Optional[torch.Tensor], buckets: torch.Tensor, eps: float,
+                  num_buckets: Optional[int] = None, want_param_grads: bool = True):
+    """Backward of ``switch_ln`` from x alone (smoe_switch_ln_bwd): (dx f32 like x, dweights f32 [K, d], dbiases f32 [K, d]); the
+    per-bucket sums are deterministic and an empty bucket's rows are exact zeros.  ``want_param_grads`` False: (dx, None, None)."""
+    _chk(x, "x", torch.float32)
+    _chk(dy, "dy", align=8)
+    dtype_code(dy.dtype)
+    d = x.shape[-1]
+    T = x.numel() // d if d else 0
+    if dy.shape != x.shape or dy.device != x.device:
+        raise RuntimeError("switch_ln_bwd: dy must have x's shape")
+    K = _switch_ln_tables(x, weights, None, None)
+    if K is None:
+        K = num_buckets
+    if K is None or not switch_ln_supported(d, K):
+        raise RuntimeError(f"switch_ln_bwd: d={d}, K={K} outside the kernel's reach")
+    _chk(buckets, "buckets", torch.int64, align=8)
+    if buckets.numel() != T or buckets.device != x.device:
+        raise RuntimeError("switch_ln_bwd: buckets must be int64 of x.shape[:-1] on x's device")
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dwb = torch.empty((2, K, d), dtype=torch.float32, device=x.device) if want_param_grads else None
+    ws_bytes = lib.smoe_switch_ln_bwd_workspace_bytes(T, d, K)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    with _timed("switch_ln_bwd", {"bytes": T * d * (12 + 2 * dy.element_size())}, x):
+        rc = lib.smoe_switch_ln_bwd(_ptr(x), _ptr(dy), dtype_code(dy.dtype), _ptr(weights), _ptr(buckets), float(eps), T, d, K, _ptr(dx),
+                                    _ptr(dwb[0]) if want_param_grads else None, _ptr(dwb[1]) if want_param_grads else None,
+                                    _ptr(ws), ws_bytes, _stream(x))
+    _lib.check(rc, "smoe_switch_ln_bwd")
+    if not want_param_grads:
+        return dx, None, None
+    return dx, dwb[0], dwb[1]

@@ -776,11 +776,12 @@ class VisionTransformer(nn.Module):
             return None
         return (int(x.shape[1]), int(self.num_tokens))
 
-    def _blocks_steps(self, x, xn0=None, head_rows_only=False):
+    def _blocks_steps(self, x, xn0=None, head_rows_only=False, blocks=None):
         """``self.blocks(x)`` as a generator, handing every block the next block's ``norm1`` so that an expert-parallel
         combine can produce it on the way out (one pass over the residual stream less per layer).  ``head_rows_only``: the
-        caller hands the result to ``_final_norm_cls`` and to nothing else (see ``_tail_rows``)."""
-        blocks = list(self.blocks)
+        caller hands the result to ``_final_norm_cls`` and to nothing else (see ``_tail_rows``).  ``blocks``: run these (a tail of
+        ``self.blocks``) instead of all of them."""
+        blocks = list(self.blocks if blocks is None else blocks)
         xn = xn0                 # norm1(x) of block 0 when the embedding pass produced it (_embed)
         for i, blk in enumerate(blocks):
             if not hasattr(blk, "forward_steps") or "forward" in blk.__dict__:   # e.g. resmoe.forward_residule_moe
@@ -920,8 +921,21 @@ def deit_tiny_patch16_224(pretrained=False, **kwargs):
 
 
 @register_model
+def deit_small_patch16_224(pretrained=False, **kwargs):
+    """models/model.py:140-160."""
+    return _deit(384, 12, 6, pretrained, **kwargs)
+
+
+@register_model
 def deit_base_patch16_224(pretrained=False, **kwargs):
     """models/model.py:163-183."""
+    return _deit(768, 12, 12, pretrained, **kwargs)
+
+
+@register_model
+def deit_base_patch16_384(pretrained=False, **kwargs):
+    """models/model.py:255-276 (N = 24 * 24 + 1 = 577 tokens: inside the attention kernels' reach)."""
+    kwargs.setdefault("img_size", 384)
     return _deit(768, 12, 12, pretrained, **kwargs)
 
 
