@@ -17,53 +17,21 @@
 //            wave w then computes  dQ^T[16 w .. 16 w + 15][32 queries] = K^T dS^T  over ALL keys (A = transposed reads
 //            of K, B = row reads of the image), so dQ needs no reduction across waves or steps and is stored at once.
 // Rows / keys >= N duplicate row N - 1 in LDS and carry P = dS = 0.  10 N^2 64 FLOP per (image, head) on the matrix cores.
-#include "smoe_common.h"
-#include <type_traits>
+#include "attention_tile.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-constexpr int AB_D = 64;
 constexpr int DS_ROW = 512;                 // bytes per query row of the dS image (up to 256 keys x 2 B)
 constexpr int DS_BYTES = 32 * DS_ROW;
 
-__device__ __forceinline__ int img_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-template <typename HT>
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, const f32x4& c) {
-  if constexpr (std::is_same<HT, f16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-template <typename HT> __device__ __forceinline__ unsigned short to16(float v) {
-  if constexpr (std::is_same<HT, f16>::value) return __builtin_bit_cast(unsigned short, (f16)v);
-  else return f32_to_bf16(v);
-}
-template <typename HT> __device__ __forceinline__ float from16(unsigned short v) {
-  if constexpr (std::is_same<HT, f16>::value) return (float)__builtin_bit_cast(f16, v);
-  else return bf16_to_f32(v);
-}
-template <typename HT> __device__ __forceinline__ u32x4 pack8(const f32x4& lo, const f32x4& hi) {
-  u32x4 r;
-  r[0] = (uint32_t)to16<HT>(lo[0]) | ((uint32_t)to16<HT>(lo[1]) << 16);
-  r[1] = (uint32_t)to16<HT>(lo[2]) | ((uint32_t)to16<HT>(lo[3]) << 16);
-  r[2] = (uint32_t)to16<HT>(hi[0]) | ((uint32_t)to16<HT>(hi[1]) << 16);
-  r[3] = (uint32_t)to16<HT>(hi[2]) | ((uint32_t)to16<HT>(hi[3]) << 16);
-  return r;
-}
-
-// two transposed reads -> the A operand [row = column idx of the 16-column block `cb`][k-slot (g, j)]: j < 4 <-> image rows
-// r_lo + j, j >= 4 <-> r_hi + (j - 4); the lane supplies row (r + tq), columns 16 cb + 4 tp .. + 3
-__device__ __forceinline__ u32x4 tr_pair(const char* img, int r_lo, int r_hi, int cb, int tq, int tp) {
-  const int chunk = 2 * cb + (tp >> 1), sub = (tp & 1) * 8;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + img_off(r_lo + tq, chunk) + sub));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + img_off(r_hi + tq, chunk) + sub));
-  s16x8 v;
+// s + the dot product of two 8-element pieces, one fma chain in element order
+template <typename HT> __device__ __forceinline__ float dot8(const u32x4& a, const u32x4& b, float s = 0.f) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) { v[r] = a[r]; v[4 + r] = b[r]; }
-  return __builtin_bit_cast(u32x4, v);
+  for (int e = 0; e < 4; ++e) {
+    s = fmaf(from16<HT>((unsigned short)(a[e] & 0xffffu)), from16<HT>((unsigned short)(b[e] & 0xffffu)), s);
+    s = fmaf(from16<HT>((unsigned short)(a[e] >> 16)), from16<HT>((unsigned short)(b[e] >> 16)), s);
+  }
+  return s;
 }
 
 template <typename HT, int NKT, int NW>
@@ -88,28 +56,19 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_bwd_kernel(const HT* __restri
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-  const int64_t ts3 = (int64_t)3 * H * AB_D, ts1 = (int64_t)H * AB_D;   // elements between tokens: qkv / o, dout
-  const HT* qbase = qkv + (int64_t)b * N * ts3 + h * AB_D;
-  const HT* obase = o + (int64_t)b * N * ts1 + h * AB_D;
-  const HT* dbase = dout + (int64_t)b * N * ts1 + h * AB_D;
-  HT* gbase = dqkv + (int64_t)b * N * ts3 + h * AB_D;
+  const int64_t ts3 = (int64_t)3 * H * ATT_D, ts1 = (int64_t)H * ATT_D;   // elements between tokens: qkv / o, dout
+  const HT* qbase = qkv + (int64_t)b * N * ts3 + h * ATT_D;
+  const HT* obase = o + (int64_t)b * N * ts1 + h * ATT_D;
+  const HT* dbase = dout + (int64_t)b * N * ts1 + h * ATT_D;
+  HT* gbase = dqkv + (int64_t)b * N * ts3 + h * ATT_D;
 
   // ---- stage Q, K, V, dO (LDS DMA, 8 rows per wave-instruction, swizzle on the source address) ------------------------------
-  {
-    const int l_row = lane >> 3, l_pos = lane & 7;
-    for (int pc = wave; pc < NR / 8; pc += NW) {
-      const int row = pc * 8 + l_row;
-      const int srow = row < N ? row : N - 1;
-      const int kc = l_pos ^ ((row >> 1) & 7);
-      const HT* p3 = qbase + (int64_t)srow * ts3 + kc * 8;
-      const HT* p1 = dbase + (int64_t)srow * ts1 + kc * 8;
-#define AB_DMA(SRC, DST) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(SRC), (__attribute__((address_space(3))) void*)(DST), 16, 0, 0)
-      AB_DMA(p3, Qs + pc * 1024);
-      AB_DMA(p3 + H * AB_D, Ks + pc * 1024);
-      AB_DMA(p3 + 2 * H * AB_D, Vs + pc * 1024);
-      AB_DMA(p1, Ds + pc * 1024);
-#undef AB_DMA
-    }
+  for (int pc = wave; pc < NR / 8; pc += NW) {
+    const HT* p3 = qbase + piece_off<false>(ts3, N, pc, lane);
+    stage_piece(Qs, pc, p3);
+    stage_piece(Ks, pc, p3 + H * ATT_D);
+    stage_piece(Vs, pc, p3 + 2 * H * ATT_D);
+    stage_piece(Ds, pc, dbase + piece_off<false>(ts1, N, pc, lane));
   }
   // the dS image starts out zero: the columns of the padding tile (keys NKT*16 .. NT*16) are never written
   for (int i = tid; i < DS_BYTES / 16; i += AB_THREADS) reinterpret_cast<u32x4*>(Si)[i] = u32x4{0u, 0u, 0u, 0u};
@@ -118,15 +77,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_bwd_kernel(const HT* __restri
     const int sq = q < N ? q : N - 1;
     float dl = 0.f;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const u32x4 ov = *reinterpret_cast<const u32x4*>(obase + (int64_t)sq * ts1 + c * 8);
-      const u32x4 dv = *reinterpret_cast<const u32x4*>(dbase + (int64_t)sq * ts1 + c * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        dl = fmaf(from16<HT>((unsigned short)(ov[e] & 0xffffu)), from16<HT>((unsigned short)(dv[e] & 0xffffu)), dl);
-        dl = fmaf(from16<HT>((unsigned short)(ov[e] >> 16)), from16<HT>((unsigned short)(dv[e] >> 16)), dl);
-      }
-    }
+    for (int c = 0; c < 8; ++c)
+      dl = dot8<HT>(*reinterpret_cast<const u32x4*>(obase + (int64_t)sq * ts1 + c * 8),
+                    *reinterpret_cast<const u32x4*>(dbase + (int64_t)sq * ts1 + c * 8), dl);
     Dl[q] = dl;
     L2[q] = lse[((int64_t)b * H + h) * N + sq];
   }
@@ -232,12 +185,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_bwd_kernel(const HT* __restri
 #pragma unroll
       for (int t = 0; t < TB; ++t) {
         const int q = q0 + 16 * (t0 + t) + li;
-        if (q < N) {
-          u32x2 pk;
-          pk[0] = (uint32_t)to16<HT>(dQ[t][0]) | ((uint32_t)to16<HT>(dQ[t][1]) << 16);
-          pk[1] = (uint32_t)to16<HT>(dQ[t][2]) | ((uint32_t)to16<HT>(dQ[t][3]) << 16);
-          *reinterpret_cast<u32x2*>(gbase + (int64_t)q * ts3 + 16 * db + 4 * g) = pk;
-        }
+        if (q < N) *reinterpret_cast<u32x2*>(gbase + (int64_t)q * ts3 + 16 * db + 4 * g) = cvt4<HT>(dQ[t]);
       }
     }
     __syncthreads();   // the image is rewritten by the next step's phase A
@@ -248,17 +196,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_bwd_kernel(const HT* __restri
     const int kt = wave + NW * i;
     const int key = kt * 16 + li;
     if (kt < NKT && key < N) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        u32x2 pk, pv;
-        pk[0] = (uint32_t)to16<HT>(dKa[i][dt][0]) | ((uint32_t)to16<HT>(dKa[i][dt][1]) << 16);
-        pk[1] = (uint32_t)to16<HT>(dKa[i][dt][2]) | ((uint32_t)to16<HT>(dKa[i][dt][3]) << 16);
-        pv[0] = (uint32_t)to16<HT>(dVa[i][dt][0]) | ((uint32_t)to16<HT>(dVa[i][dt][1]) << 16);
-        pv[1] = (uint32_t)to16<HT>(dVa[i][dt][2]) | ((uint32_t)to16<HT>(dVa[i][dt][3]) << 16);
-        HT* kp = gbase + (int64_t)key * ts3 + H * AB_D + 16 * dt + 4 * g;
-        *reinterpret_cast<u32x2*>(kp) = pk;
-        *reinterpret_cast<u32x2*>(kp + H * AB_D) = pv;
-      }
+      HT* kp = gbase + (int64_t)key * ts3 + H * ATT_D + 4 * g;
+      store_tile(kp, dKa[i]);
+      store_tile(kp + H * ATT_D, dVa[i]);
     }
   }
 }
@@ -293,16 +233,6 @@ constexpr int ABL_KB = 128;                               // keys per workgroup 
 constexpr int ABL_STEP = 2 * 32 * 128 + 2 * 32 * 4;       // a staged step: Q and dO images of 32 queries, their lse and delta
 constexpr int ABL_CH = 4;                                 // key tiles per chunk of the dQ kernel
 
-template <typename HT> __device__ __forceinline__ float dot8(const u32x4& a, const u32x4& b) {
-  float s = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    s = fmaf(from16<HT>((unsigned short)(a[e] & 0xffffu)), from16<HT>((unsigned short)(b[e] & 0xffffu)), s);
-    s = fmaf(from16<HT>((unsigned short)(a[e] >> 16)), from16<HT>((unsigned short)(b[e] >> 16)), s);
-  }
-  return s;
-}
-
 template <typename HT>
 __global__ __launch_bounds__(ABL_THREADS, 4) void attn_bwd_dkv_kernel(const HT* __restrict__ qkv, const HT* __restrict__ o,
                                                                       const HT* __restrict__ dout, const float* __restrict__ lse,
@@ -313,12 +243,12 @@ __global__ __launch_bounds__(ABL_THREADS, 4) void attn_bwd_dkv_kernel(const HT* 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-  const int64_t ts3 = (int64_t)3 * H * AB_D, ts1 = (int64_t)H * AB_D;
-  const HT* qbase = qkv + (int64_t)b * N * ts3 + h * AB_D;
-  const HT* obase = o + (int64_t)b * N * ts1 + h * AB_D;
-  const HT* dbase = dout + (int64_t)b * N * ts1 + h * AB_D;
+  const int64_t ts3 = (int64_t)3 * H * ATT_D, ts1 = (int64_t)H * ATT_D;
+  const HT* qbase = qkv + (int64_t)b * N * ts3 + h * ATT_D;
+  const HT* obase = o + (int64_t)b * N * ts1 + h * ATT_D;
+  const HT* dbase = dout + (int64_t)b * N * ts1 + h * ATT_D;
   const float* lbase = lse + ((int64_t)b * H + h) * N;
-  HT* gbase = dqkv + (int64_t)b * N * ts3 + h * AB_D;
+  HT* gbase = dqkv + (int64_t)b * N * ts3 + h * ATT_D;
 
   // the wave's key tile: K / V row fragments straight from memory (keys >= N duplicate row N - 1 and carry P = dS = 0)
   const int kt = kb * (ABL_KB / 16) + wave;
@@ -327,11 +257,11 @@ __global__ __launch_bounds__(ABL_THREADS, 4) void attn_bwd_dkv_kernel(const HT* 
   const bool tile_live = kt * 16 < N;      // wave-uniform
   u32x4 kf[2], vf[2];
   {
-    const HT* kp = qbase + (int64_t)(kvalid ? key : N - 1) * ts3 + H * AB_D + g * 8;
+    const HT* kp = qbase + (int64_t)(kvalid ? key : N - 1) * ts3 + H * ATT_D + g * 8;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       kf[kk] = *reinterpret_cast<const u32x4*>(kp + 32 * kk);
-      vf[kk] = *reinterpret_cast<const u32x4*>(kp + H * AB_D + 32 * kk);
+      vf[kk] = *reinterpret_cast<const u32x4*>(kp + H * ATT_D + 32 * kk);
     }
   }
   // staging roles: waves 0-3 carry the Q image of a step (one 16-byte piece per thread), waves 4-7 the dO image, the O piece next
@@ -440,17 +370,9 @@ __global__ __launch_bounds__(ABL_THREADS, 4) void attn_bwd_dkv_kernel(const HT* 
     __syncthreads();
   }
   if (kvalid) {
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      u32x2 pk, pv;
-      pk[0] = (uint32_t)to16<HT>(dKa[dt][0]) | ((uint32_t)to16<HT>(dKa[dt][1]) << 16);
-      pk[1] = (uint32_t)to16<HT>(dKa[dt][2]) | ((uint32_t)to16<HT>(dKa[dt][3]) << 16);
-      pv[0] = (uint32_t)to16<HT>(dVa[dt][0]) | ((uint32_t)to16<HT>(dVa[dt][1]) << 16);
-      pv[1] = (uint32_t)to16<HT>(dVa[dt][2]) | ((uint32_t)to16<HT>(dVa[dt][3]) << 16);
-      HT* kp = gbase + (int64_t)key * ts3 + H * AB_D + 16 * dt + 4 * g;
-      *reinterpret_cast<u32x2*>(kp) = pk;
-      *reinterpret_cast<u32x2*>(kp + H * AB_D) = pv;
-    }
+    HT* kp = gbase + (int64_t)key * ts3 + H * ATT_D + 4 * g;
+    store_tile(kp, dKa);
+    store_tile(kp + H * ATT_D, dVa);
   }
 }
 
@@ -467,26 +389,18 @@ __global__ __launch_bounds__(ABL_THREADS, 1) void attn_bwd_dq_kernel(const HT* _
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-  const int64_t ts3 = (int64_t)3 * H * AB_D, ts1 = (int64_t)H * AB_D;
-  const HT* qbase = qkv + (int64_t)b * N * ts3 + h * AB_D;
-  const HT* obase = o + (int64_t)b * N * ts1 + h * AB_D;
-  const HT* dbase = dout + (int64_t)b * N * ts1 + h * AB_D;
+  const int64_t ts3 = (int64_t)3 * H * ATT_D, ts1 = (int64_t)H * ATT_D;
+  const HT* qbase = qkv + (int64_t)b * N * ts3 + h * ATT_D;
+  const HT* obase = o + (int64_t)b * N * ts1 + h * ATT_D;
+  const HT* dbase = dout + (int64_t)b * N * ts1 + h * ATT_D;
   const float* lbase = lse + ((int64_t)b * H + h) * N;
-  HT* gbase = dqkv + (int64_t)b * N * ts3 + h * AB_D;
+  HT* gbase = dqkv + (int64_t)b * N * ts3 + h * ATT_D;
   // ---- stage K and V of the head (LDS DMA, 8 rows per wave-instruction, swizzle on the source address; both images in the
   //      row-read layout of img_off: K is read by rows AND transposed, V by rows only) ------------------------------------------------
-  {
-    const int l_row = lane >> 3, l_pos = lane & 7;
-    for (int pc = wave; pc < nkt_pad * 2; pc += ABL_THREADS / 64) {
-      const int row = pc * 8 + l_row;
-      const int srow = row < N ? row : N - 1;
-      const int kc = l_pos ^ ((row >> 1) & 7);
-      const HT* p3 = qbase + (int64_t)srow * ts3 + H * AB_D + kc * 8;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p3),
-                                       (__attribute__((address_space(3))) void*)(Ks + pc * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p3 + H * AB_D),
-                                       (__attribute__((address_space(3))) void*)(Vs + pc * 1024), 16, 0, 0);
-    }
+  for (int pc = wave; pc < nkt_pad * 2; pc += ABL_THREADS / 64) {
+    const HT* p3 = qbase + H * ATT_D + piece_off<false>(ts3, N, pc, lane);
+    stage_piece(Ks, pc, p3);
+    stage_piece(Vs, pc, p3 + H * ATT_D);
   }
   const int nqt = (N + 15) >> 4;
   const int nchunk = nkt_pad / ABL_CH;
@@ -494,17 +408,11 @@ __global__ __launch_bounds__(ABL_THREADS, 1) void attn_bwd_dq_kernel(const HT* _
   // the lane's query (the 4 lanes that share a query each sum a quarter of dO O)
   struct Tile { u32x4 q0, q1, d0, d1; float l2, dl; };
   auto load_tile = [&](int qt, Tile& t) {
-    int qrow = qt * 16 + li;
-    if (qrow >= N) qrow = N - 1;
-    const HT* qp = qbase + (int64_t)qrow * ts3 + g * 8;
-    const HT* dp = dbase + (int64_t)qrow * ts1 + g * 8;
-    const HT* op = obase + (int64_t)qrow * ts1 + g * 8;
-    t.q0 = *reinterpret_cast<const u32x4*>(qp);
-    t.q1 = *reinterpret_cast<const u32x4*>(qp + 32);
-    t.d0 = *reinterpret_cast<const u32x4*>(dp);
-    t.d1 = *reinterpret_cast<const u32x4*>(dp + 32);
-    const u32x4 o0 = *reinterpret_cast<const u32x4*>(op), o1 = *reinterpret_cast<const u32x4*>(op + 32);
-    t.l2 = lbase[qrow];
+    u32x4 o0, o1;
+    load_q(qbase, ts3, N, qt, li, g, t.q0, t.q1);
+    load_q(dbase, ts1, N, qt, li, g, t.d0, t.d1);
+    load_q(obase, ts1, N, qt, li, g, o0, o1);
+    t.l2 = lbase[min(qt * 16 + li, N - 1)];
     float dl = dot8<HT>(o0, t.d0) + dot8<HT>(o1, t.d1);
     dl += __shfl_xor(dl, 16, 64);
     dl += __shfl_xor(dl, 32, 64);
@@ -562,15 +470,7 @@ __global__ __launch_bounds__(ABL_THREADS, 1) void attn_bwd_dq_kernel(const HT* _
     }
     // ---- store: lane (g, li) holds head-dim elements 16 dt + 4 g + r of query 16 qt + li ------------------------------------------
     const int q = qt * 16 + li;
-    if (q < N) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        u32x2 pk;
-        pk[0] = (uint32_t)to16<HT>(dq[dt][0]) | ((uint32_t)to16<HT>(dq[dt][1]) << 16);
-        pk[1] = (uint32_t)to16<HT>(dq[dt][2]) | ((uint32_t)to16<HT>(dq[dt][3]) << 16);
-        *reinterpret_cast<u32x2*>(gbase + (int64_t)q * ts3 + 16 * dt + 4 * g) = pk;
-      }
-    }
+    if (q < N) store_tile(gbase + (int64_t)q * ts3 + 4 * g, dq);
   }
 }
 
@@ -615,7 +515,7 @@ int bwd_dispatch(const void* qkv, const void* o, const void* dout, const float* 
 
 }  // namespace
 
-extern "C" int smoe_attention_bwd_supported(int N, int head_dim) { return (N >= 1 && N <= 640 && head_dim == AB_D) ? 1 : 0; }
+extern "C" int smoe_attention_bwd_supported(int N, int head_dim) { return (N >= 1 && N <= 640 && head_dim == ATT_D) ? 1 : 0; }
 
 // qkv, dqkv [B, N, 3, H, 64]; o, dout [B, N, H*64]; lse [B, H, N] f32 from smoe_attention_fwd; f16 or bf16
 extern "C" int smoe_attention_bwd(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, int dtype, int B,

@@ -6,23 +6,15 @@
 // Three kernels:
 //   smoe_skip_plan             mask -> per-image (row_start, len, mult), the compact gather list, the projection's row map, the
 //                              one-group offsets [0, R] and every bypassed token's representative output row -- all on the device
-//   smoe_attention_fwd_varlen  attention.hip's one-pass forward over the compact qkv, row range and key count per image from the
+//   smoe_attention_fwd_varlen  the one-pass forward (attention_tile.h) over the compact qkv, row range and key count per image from the
 //                              plan, the last key of an image weighted by mult
 //   smoe_skip_expand           out[t] = xn32[t] + out[rep_row[t]] for the bypassed tokens
 // No allocation, no synchronisation, no float atomics; every output is a pure function of the inputs.
-#include "smoe_common.h"
-#include <type_traits>
+#include "attention_tile.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-constexpr int ATT_D = 64;
-constexpr int ATT_THREADS = 256;
 constexpr int PLAN_THREADS = 256;
-
-// the LDS layouts of attention.hip (K: 16-byte chunk swizzle, V: 32-byte segment swizzle)
-__device__ __forceinline__ int k_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int v_lds_off(int row, int dt) { return row * 128 + ((dt ^ ((row >> 1) & 3)) << 5); }
 
 // ---- plan ----------------------------------------------------------------------------------------------------------------------
 // pass 1, one workgroup per image: len[b] = n_b + (m_b > 0), mult[b] = m_b; the parked output row of the image is zeroed (it is
@@ -133,207 +125,9 @@ __global__ __launch_bounds__(256) void skip_expand_kernel(const float* xn32, con
 }
 
 // ---- varlen attention ------------------------------------------------------------------------------------------------------------
-// attention.hip's attn_fwd_kernel for one (image, head) whose rows are base[0 .. len): NKT key tiles of 16 held in LDS (NKT * 16 >=
-// len), key index >= len masked at run time -- only the tiles from the last real one on carry mask code (a wave-uniform branch per
-// tile).  The last key counts `mult` times: its probability is multiplied by wmul after the exponential (exact for an integer in f32;
-// the normaliser is the matrix-pipe sum of the same rounded values), or -- SMOE_VARLEN_WEIGHT_SCORE -- log2(mult) is added to its
-// scaled score in front of the maximum.
-template <typename HT, int NKT>
-__device__ __forceinline__ void attn_varlen_body(char* smem, const HT* __restrict__ base, HT* __restrict__ obase, int len, int H,
-                                                 float scale_log2e, float wmul_last, float wadd_last) {
-  constexpr int NT = NKT + (NKT & 1);
-  constexpr int nkt = NKT;
-  char* Ks = smem;
-  char* Vs = smem + nkt * 16 * 128;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t tok_stride = (int64_t)3 * H * ATT_D;
-  // stage K and V by LDS DMA; rows >= len duplicate row len - 1 (masked below: probability exactly 0)
-  {
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int l_row = lane >> 3, l_pos = lane & 7;
-    const int npieces = nkt * 2;
-    for (int pc = wave_u; pc < npieces; pc += ATT_THREADS / 64) {
-      const int row = pc * 8 + l_row;
-      const int srow = row < len ? row : len - 1;
-      const HT* p = base + (int64_t)srow * tok_stride;
-      const int kc = l_pos ^ ((row >> 1) & 7);
-      const int vc = (((l_pos >> 1) ^ ((row >> 1) & 3)) << 1) | (l_pos & 1);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + H * ATT_D + kc * 8),
-                                       (__attribute__((address_space(3))) void*)(Ks + pc * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + 2 * H * ATT_D + vc * 8),
-                                       (__attribute__((address_space(3))) void*)(Vs + pc * 1024), 16, 0, 0);
-    }
-  }
-  const int g = lane >> 4, qi = lane & 15;
-  const int nqt = (len + 15) >> 4;
-  auto load_q = [&](int qt, u32x4& f0, u32x4& f1) {
-    int qrow = qt * 16 + qi;
-    if (qrow >= len) qrow = len - 1;
-    const HT* qp = base + (int64_t)qrow * tok_stride + g * 8;
-    f0 = *reinterpret_cast<const u32x4*>(qp);
-    f1 = *reinterpret_cast<const u32x4*>(qp + 32);
-  };
-  u32x4 qn0 = u32x4{0u, 0u, 0u, 0u}, qn1 = qn0;
-  if (wave < nqt) load_q(wave, qn0, qn1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  // the weighted key: slot (g, r) of tile kt_last
-  const int last = len - 1;
-  const int kt_last = __builtin_amdgcn_readfirstlane(last >> 4);
-  float wmul[4], wadd[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const bool is_last = (g * 4 + r) == (last & 15);
-    wmul[r] = is_last ? wmul_last : 1.0f;
-    wadd[r] = is_last ? wadd_last : 0.0f;
-  }
-  for (int qt = wave; qt < nqt; qt += ATT_THREADS / 64) {
-    const int q0 = qt * 16;
-    const u32x4 qf0 = qn0, qf1 = qn1;
-    if (qt + ATT_THREADS / 64 < nqt) load_q(qt + ATT_THREADS / 64, qn0, qn1);
-    f32x4 sacc[NT];
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) sacc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr int NKG = (nkt + 3) / 4;
-    u32x4 kf[2][4][2];
-    auto read_k = [&](int buf, int kg) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (kg + i < nkt) {
-          kf[buf][i][0] = *reinterpret_cast<const u32x4*>(Ks + k_lds_off((kg + i) * 16 + qi, g));
-          kf[buf][i][1] = *reinterpret_cast<const u32x4*>(Ks + k_lds_off((kg + i) * 16 + qi, 4 + g));
-        }
-      }
-    };
-    read_k(0, 0);
-#pragma unroll
-    for (int gi = 0; gi < NKG; ++gi) {
-      const int kg = gi * 4;
-      if (gi + 1 < NKG) read_k((gi + 1) & 1, kg + 4);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (kg + i < nkt) {
-            if constexpr (std::is_same<HT, f16>::value)
-              sacc[kg + i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[gi & 1][i][hf]), __builtin_bit_cast(f16x8, hf ? qf1 : qf0), sacc[kg + i], 0, 0, 0);
-            else
-              sacc[kg + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf[gi & 1][i][hf]), __builtin_bit_cast(bf16x8_t, hf ? qf1 : qf0), sacc[kg + i], 0, 0, 0);
-          }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // keys >= len: -inf; the weighted key's score shift (0 unless the weight rides on the score)
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      if (kt >= kt_last) {  // wave-uniform
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (kt == kt_last) sacc[kt][r] += wadd[r];
-          if (kt * 16 + g * 4 + r >= len) sacc[kt][r] = -INFINITY;
-        }
-      }
-    }
-    float mm[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      mm[(2 * kt) & 3] = fmaxf(fmaxf(mm[(2 * kt) & 3], sacc[kt][0]), sacc[kt][1]);
-      mm[(2 * kt + 1) & 3] = fmaxf(fmaxf(mm[(2 * kt + 1) & 3], sacc[kt][2]), sacc[kt][3]);
-    }
-    float m = fmaxf(fmaxf(mm[0], mm[1]), fmaxf(mm[2], mm[3]));
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const float nmc = -m * scale_log2e;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sacc[kt][r] = __builtin_amdgcn_exp2f(fmaf(sacc[kt][r], scale_log2e, nmc));
-      if (kt == kt_last) {  // wave-uniform: the weighted key's probability counts mult times
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sacc[kt][r] *= wmul[r];
-      }
-    }
-    u32x4 pf[NT / 2];
-#pragma unroll
-    for (int ks = 0; ks < NT / 2; ++ks) {
-      if constexpr (std::is_same<HT, f16>::value) {
-        f16x8 t;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { t[r] = (f16)sacc[2 * ks][r]; t[4 + r] = (2 * ks + 1 < NKT) ? (f16)sacc[2 * ks + 1][r] : (f16)0.f; }
-        pf[ks] = __builtin_bit_cast(u32x4, t);
-      } else {
-        s16x8 t;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { t[r] = (short)f32_to_bf16(sacc[2 * ks][r]); t[4 + r] = (2 * ks + 1 < NKT) ? (short)f32_to_bf16(sacc[2 * ks + 1][r]) : (short)0; }
-        pf[ks] = __builtin_bit_cast(u32x4, t);
-      }
-    }
-    f32x4 oacc[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 lacc = f32x4{0.f, 0.f, 0.f, 0.f};
-    const u32x4 ones = std::is_same<HT, f16>::value ? u32x4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u}
-                                                    : u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
-    const int tq = qi >> 2, tp = qi & 3;
-    s16x4 v0[2][4], v1[2][4];
-    auto read_v = [&](int buf, int ks) {
-      const int row1 = 32 * ks + 4 * g + tq;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        v0[buf][dt] = s16x4{0, 0, 0, 0};
-        v1[buf][dt] = s16x4{0, 0, 0, 0};
-        if (2 * ks < nkt)
-          v0[buf][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) s16x4*)(Vs + v_lds_off(row1, dt) + tp * 8));
-        if (2 * ks + 1 < nkt)
-          v1[buf][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) s16x4*)(Vs + v_lds_off(row1 + 16, dt) + tp * 8));
-      }
-    };
-    read_v(0, 0);
-#pragma unroll
-    for (int ks = 0; ks < NT / 2; ++ks) {
-      if (ks + 1 < NT / 2) read_v((ks + 1) & 1, ks + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        s16x8 vf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { vf[r] = v0[ks & 1][dt][r]; vf[4 + r] = v1[ks & 1][dt][r]; }
-        if constexpr (std::is_same<HT, f16>::value)
-          oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, vf), __builtin_bit_cast(f16x8, pf[ks]), oacc[dt], 0, 0, 0);
-        else
-          oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[ks]), oacc[dt], 0, 0, 0);
-      }
-      if constexpr (std::is_same<HT, f16>::value)
-        lacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ones), __builtin_bit_cast(f16x8, pf[ks]), lacc, 0, 0, 0);
-      else
-        lacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ones), __builtin_bit_cast(bf16x8_t, pf[ks]), lacc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    const float inv_l = 1.0f / lacc[0];
-    if (q0 + qi < len) {
-      HT* op = obase + (int64_t)(q0 + qi) * (H * ATT_D) + g * 4;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        if constexpr (std::is_same<HT, f16>::value) {
-          f16x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (f16)(oacc[dt][r] * inv_l);
-          *reinterpret_cast<f16x4*>(op + dt * 16) = o;
-        } else {
-          s16x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (short)f32_to_bf16(oacc[dt][r] * inv_l);
-          *reinterpret_cast<s16x4*>(op + dt * 16) = o;
-        }
-      }
-    }
-  }
-}
-
+// attention_tile.h's attn_fwd_body with MASK_LEN: the rows of an (image, head) are base[0 .. len), key index >= len is masked at run
+// time, the last key counts `mult` times (by default on its probability; SMOE_VARLEN_WEIGHT_SCORE: log2(mult) on its scaled score);
+// no lse.
 // One workgroup per (image, head).  NKTMAX covers the caller's max_len; with tiers an image takes the smallest instantiated key-tile
 // count that holds its own len (a workgroup-uniform choice: same launch, fewer score registers walked for short images).
 template <typename HT, int NKTMAX>
@@ -358,10 +152,10 @@ __global__ __launch_bounds__(ATT_THREADS, 3) void attn_varlen_kernel(const HT* _
     else wmul = (float)mult;
   }
   const bool tiers = !(flags & SMOE_VARLEN_NO_TIERS);
-  if (NKTMAX > 4 && tiers && len <= 64) attn_varlen_body<HT, 4>(smem, base, obase, len, H, scale_log2e, wmul, wadd);
-  else if (NKTMAX > 8 && tiers && len <= 128) attn_varlen_body<HT, 8>(smem, base, obase, len, H, scale_log2e, wmul, wadd);
-  else if (NKTMAX > 13 && tiers && len <= 208) attn_varlen_body<HT, 13>(smem, base, obase, len, H, scale_log2e, wmul, wadd);
-  else attn_varlen_body<HT, NKTMAX>(smem, base, obase, len, H, scale_log2e, wmul, wadd);
+  if (NKTMAX > 4 && tiers && len <= 64) attn_fwd_body<HT, 4, MASK_LEN>(smem, base, obase, nullptr, len, H, scale_log2e, wmul, wadd);
+  else if (NKTMAX > 8 && tiers && len <= 128) attn_fwd_body<HT, 8, MASK_LEN>(smem, base, obase, nullptr, len, H, scale_log2e, wmul, wadd);
+  else if (NKTMAX > 13 && tiers && len <= 208) attn_fwd_body<HT, 13, MASK_LEN>(smem, base, obase, nullptr, len, H, scale_log2e, wmul, wadd);
+  else attn_fwd_body<HT, NKTMAX, MASK_LEN>(smem, base, obase, nullptr, len, H, scale_log2e, wmul, wadd);
 }
 
 template <typename HT, int NKTMAX>

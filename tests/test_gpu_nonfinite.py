@@ -45,11 +45,11 @@ F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
 EXCEPTIONS = [
     # observed on an MI355X at N = 257 / 577 / 640, f16 and bf16: -inf in column 11 of keys 0..159 for the queries with q[11] > 0 ...
     ("attn_fwd", "k[first chunk,col 11]", "-inf",
-     "slim-switch-moe-vit_amd/csrc/attention.hip:339-340: when every score of the first 160-key chunk is -inf the running maximum "
+     "slim-switch-moe-vit_amd/csrc/attention.hip:104-105: when every score of the first 160-key chunk is -inf the running maximum "
      "stays -inf and the rescale factor exp2((-inf) - (-inf)) is NaN; float64 softmax gives those keys probability 0"),
     # ... and +inf there for the queries with q[11] < 0 (their scores are -inf as well)
     ("attn_fwd", "k[first chunk,col 11]", "+inf",
-     "slim-switch-moe-vit_amd/csrc/attention.hip:339-340: the same all -inf first chunk, reached through (+inf) x (a negative q[11])"),
+     "slim-switch-moe-vit_amd/csrc/attention.hip:104-105: the same all -inf first chunk, reached through (+inf) x (a negative q[11])"),
 ]
 _exceptions_used = set()
 _cases_run = [0]

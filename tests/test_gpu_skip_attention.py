@@ -100,15 +100,20 @@ def test_varlen_attention_against_float64_within_three_times_the_existing_kernel
 
 
 def test_varlen_attention_same_bits_on_every_call_and_full_images_against_the_existing_kernel():
-    """Reported, not required: with mult = 0 and every len = N the varlen kernel walks the existing kernel's arithmetic."""
-    H, N, B = 3, 197, 3
-    qkv = torch.randn(B * N, 3, H, 64, generator=torch.Generator().manual_seed(5)).half()
-    a = _varlen_run(qkv, [N] * B, [0] * B, H)
-    b = _varlen_run(qkv, [N] * B, [0] * B, H)
-    assert torch.equal(a, b)
-    old = ops.attention(qkv.reshape(B * N, -1).to(DEV), B, N, H, 64, 0.125).cpu().reshape(B * N, H * 64)
-    print("varlen (mult = 0, len = N = 197) bit-equal to smoe_attention_fwd:", torch.equal(a, old),
-          "max |diff| =", (a.float() - old.float()).abs().max().item())
+    """With mult = 0 and every len = N the varlen kernel walks the dense kernel's arithmetic -- the two are one body
+    (csrc/attention_tile.h: attn_fwd_body) under different mask policies, so their outputs are the same bits.  N on both sides of every
+    key-tile count the two dispatchers instantiate (4, 8, 13, 16 tiles of 16 keys), both dtypes."""
+    H, B = 3, 2
+    for dt in (torch.float16, torch.bfloat16):
+        for N in (16, 17, 64, 65, 197, 208, 256):
+            qkv = torch.randn(B * N, 3, H, 64, generator=torch.Generator().manual_seed(5 + N)).to(dt)
+            a = _varlen_run(qkv, [N] * B, [0] * B, H)
+            b = _varlen_run(qkv, [N] * B, [0] * B, H)
+            assert torch.equal(a, b), (dt, N, "same bits on every call")
+            old = ops.attention(qkv.reshape(B * N, -1).to(DEV), B, N, H, 64, 0.125).cpu().reshape(B * N, H * 64)
+            print(f"varlen (mult = 0, len = N = {N}, {dt}) bit-equal to smoe_attention_fwd:", torch.equal(a, old),
+                  "max |diff| =", (a.float() - old.float()).abs().max().item())
+            assert torch.equal(a, old), (dt, N)
 
 
 # ----------------------------------------------------------------------------------------------------------------------- expand
