@@ -9,20 +9,53 @@
 // variance, as the forward kernel) -- nothing but x itself is saved by the forward.  Bound: HBM (x + dy read, dx written).
 // The column sums are deterministic: every wave keeps its own partial sums in registers over the rows it walks, the
 // four waves of a workgroup meet in LDS in wave order, every workgroup writes one partial row, and a second launch adds
-// the partial rows in workgroup order (no atomics).
-#include "smoe_common.h"
-#include <type_traits>
+// the partial rows in workgroup order (no atomics).  The layout and every step two kernels of it share: wave_row4.h.
+#include "wave_row4.h"
+
+namespace {
+
+// out_a[blockIdx.y][c] (c < L) = sum over the partial rows [blockIdx.y * rows_per_block, +rows_per_block) in row order.  A workgroup
+// takes 32 columns (one 128-byte segment of every partial row); thread (column c, slice r of 8) adds rows r, r + 8, ... in order, the
+// eight slices meet in LDS in slice order: deterministic, and the 6-MB table is read at streaming rate (the first version gave every
+// column to one thread walking all 1,024 rows: 226 us per call, 10 % of the training step).  Columns from `split` on go to out_b
+// (SwitchableLayerNorm's last stage writes dweights and dbiases apart).
+__global__ __launch_bounds__(256) void wr4_reduce_kernel(const float* __restrict__ partial, int n_rows, int L, int rows_per_block,
+                                                         float* __restrict__ out_a, int split, float* __restrict__ out_b) {
+  __shared__ float red[8][32];
+  const int c = blockIdx.x * 32 + (threadIdx.x & 31), r = threadIdx.x >> 5;
+  const int row0 = blockIdx.y * rows_per_block;
+  int row1 = row0 + rows_per_block;
+  if (row1 > n_rows) row1 = n_rows;
+  float s = 0.f;
+  if (c < L)
+    for (int row = row0 + r; row < row1; row += 8) s += partial[(int64_t)row * L + c];
+  red[r][threadIdx.x & 31] = s;
+  __syncthreads();
+  if (r == 0 && c < L) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t += red[i][threadIdx.x & 31];
+    if (c < split) out_a[(int64_t)blockIdx.y * L + c] = t;
+    else out_b[c - split] = t;
+  }
+}
+
+}  // namespace
+
+// Two stages (WR4_STAGE1 = 16 row groups, then one): with the whole table behind 48 workgroups one stage still took 38 us per call --
+// 128 dependent-latency trips per thread on a fifth of the chip (profiles/r03_dispatch_kernels.md).
+void wr4_reduce_partials(float* partial, int n_rows, int L, float* out_a, int split, float* out_b, hipStream_t s) {
+  float* stage1 = partial + (size_t)n_rows * L;
+  const int rpb = (n_rows + WR4_STAGE1 - 1) / WR4_STAGE1;
+  hipLaunchKernelGGL(wr4_reduce_kernel, dim3((L + 31) / 32, WR4_STAGE1), dim3(256), 0, s, partial, n_rows, L, rpb, stage1, L,
+                     (float*)nullptr);
+  hipLaunchKernelGGL(wr4_reduce_kernel, dim3((L + 31) / 32, 1), dim3(256), 0, s, stage1, WR4_STAGE1, L, WR4_STAGE1, out_a, split, out_b);
+}
 
 namespace {
 
 constexpr int LNB_THREADS = 256;
 constexpr int LNB_WAVES = LNB_THREADS / 64;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 template <typename DYT, int NJ>
 __global__ __launch_bounds__(LNB_THREADS) void layernorm_bwd_kernel(const float* __restrict__ x, const DYT* __restrict__ dy,
@@ -30,13 +63,9 @@ __global__ __launch_bounds__(LNB_THREADS) void layernorm_bwd_kernel(const float*
                                                                     float eps, int64_t T, int d, float* __restrict__ dx,
                                                                     float* __restrict__ partial) {
   __shared__ float red[LNB_WAVES][2][NJ * 256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nchunk = d >> 2;
-  float ag[NJ][4], ab[NJ][4];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ag[j][i] = ab[j][i] = 0.f;
+  float acc[2][NJ][4] = {};     // dgamma, dbeta
   f32x4 gm[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -47,43 +76,21 @@ __global__ __launch_bounds__(LNB_THREADS) void layernorm_bwd_kernel(const float*
   const int64_t row0 = (int64_t)blockIdx.x * LNB_WAVES + wave, stride = (int64_t)gridDim.x * LNB_WAVES;
   for (int64_t t = row0; t < T; t += stride) {
     float xv[NJ][4], gv[NJ][4];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int c = lane + 64 * j;
-      if (c < nchunk) {
-        load4(x + t * (int64_t)d + c * 4, xv[j]);
-        load4(dy + t * (int64_t)d + c * 4, gv[j]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xv[j][i] = gv[j][i] = 0.f;
-      }
-    }
-    float s1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) s1 += (xv[j][0] + xv[j][1]) + (xv[j][2] + xv[j][3]);
-    const float mean = wave_sum(s1) * inv_d;
-    float s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      if (lane + 64 * j < nchunk) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const float dv = xv[j][i] - mean; s2 = fmaf(dv, dv, s2); }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(s2) * inv_d + eps);
+    wr4_load(nchunk, lane, wr4_row(x + t * (int64_t)d, xv), wr4_row(dy + t * (int64_t)d, gv));
+    float mean, rstd;
+    wr4_row_stats<false, NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float xh = (lane + 64 * j < nchunk) ? (xv[j][i] - mean) * rstd : 0.f;
         const float dyv = gv[j][i];
-        ag[j][i] = fmaf(dyv, xh, ag[j][i]);     // dgamma
-        ab[j][i] += dyv;                        // dbeta
+        xv[j][i] = (lane + 64 * j < nchunk) ? (xv[j][i] - mean) * rstd : 0.f;
+        acc[0][j][i] = fmaf(dyv, xv[j][i], acc[0][j][i]);
+        acc[1][j][i] += dyv;
         const float g = dyv * gm[j][i];
         c1 += g;
-        c2 = fmaf(g, xh, c2);
-        xv[j][i] = xh;
+        c2 = fmaf(g, xv[j][i], c2);
         gv[j][i] = g;
       }
     }
@@ -101,22 +108,7 @@ __global__ __launch_bounds__(LNB_THREADS) void layernorm_bwd_kernel(const float*
       }
     }
   }
-  // the workgroup's column sums, waves added in wave order
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      red[wave][0][(lane + 64 * j) * 4 + i] = ag[j][i];
-      red[wave][1][(lane + 64 * j) * 4 + i] = ab[j][i];
-    }
-  __syncthreads();
-  for (int c = tid; c < 2 * d; c += LNB_THREADS) {
-    const int which = c >= d, col = which ? c - d : c;
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < LNB_WAVES; ++w) s += red[w][which][col];
-    partial[(int64_t)blockIdx.x * 2 * d + c] = s;
-  }
+  wr4_flush_cols<2, NJ, LNB_WAVES>(red, acc, d, partial + (int64_t)blockIdx.x * 2 * d);
 }
 
 // One gated half of the residual-MoE block, backward, in ONE pass (models/resMoE.py:126-131 / 137-140 with Gate.forward's hard
@@ -143,15 +135,11 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunk = d >> 2;
   const int L = 3 * d + 4;
-  float ag[NJ][4], ab[NJ][4], aw[NJ][4];
+  float acc[3][NJ][4] = {};     // dgamma, dbeta, dgate_w
   float agb = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ag[j][i] = ab[j][i] = aw[j][i] = 0.f;
   f32x4 gm[NJ], bt[NJ], wv[NJ];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
+  for (int j = 0; j < NJ; ++j) {     // (gamma / beta / w per lane: as a helper of wave_row4.h this loop cost 7 - 17 VGPRs)
     const int c = lane + 64 * j;
     const bool in = c < nchunk;
     gm[j] = (gamma && in) ? *reinterpret_cast<const f32x4*>(gamma + c * 4) : f32x4{1.f, 1.f, 1.f, 1.f};
@@ -164,7 +152,7 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
   for (int64_t t = row0; t < T; t += stride) {
     float xv[NJ][4], gv[NJ][4], go[NJ][4];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < NJ; ++j) {     // (its own row load, g_out optional: through wr4_load the NJ = 3 kernels took 5 more VGPRs)
       const int c = lane + 64 * j;
       if (c < nchunk) {
         load4(x + t * (int64_t)d + c * 4, xv[j]);
@@ -177,19 +165,8 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
       }
     }
     const float keep = gate_on ? mask[t * 2 + 1] : 1.f;
-    float s1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) s1 += (xv[j][0] + xv[j][1]) + (xv[j][2] + xv[j][3]);
-    const float mean = wave_sum(s1) * inv_d;
-    float s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      if (lane + 64 * j < nchunk) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const float dv = xv[j][i] - mean; s2 = fmaf(dv, dv, s2); }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(s2) * inv_d + eps);
+    float mean, rstd;
+    wr4_row_stats<false, NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
     // the gate: logit and <g_f, xn> on the recomputed normed row (xv becomes xhat, xn kept beside it)
     float xn[NJ][4];
     float az = 0.f, ad = 0.f;
@@ -198,9 +175,8 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
       const bool in = lane + 64 * j < nchunk;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float xh = in ? (xv[j][i] - mean) * rstd : 0.f;
-        xv[j][i] = xh;
-        xn[j][i] = in ? fmaf(xh, gm[j][i], bt[j][i]) : 0.f;
+        xv[j][i] = in ? (xv[j][i] - mean) * rstd : 0.f;
+        xn[j][i] = in ? fmaf(xv[j][i], gm[j][i], bt[j][i]) : 0.f;
         az = fmaf(xn[j][i], wv[j][i], az);
         ad = fmaf(gv[j][i], xn[j][i], ad);
       }
@@ -218,9 +194,9 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
       for (int i = 0; i < 4; ++i) {
         const float dyv = fmaf(gv[j][i], keep, fmaf(dz, wv[j][i], go[j][i]));     // dxn
         const float xh = xv[j][i];
-        ag[j][i] = fmaf(dyv, xh, ag[j][i]);
-        ab[j][i] += dyv;
-        aw[j][i] = fmaf(dz, xn[j][i], aw[j][i]);
+        acc[0][j][i] = fmaf(dyv, xh, acc[0][j][i]);
+        acc[1][j][i] += dyv;
+        acc[2][j][i] = fmaf(dz, xn[j][i], acc[2][j][i]);
         const float g = dyv * gm[j][i];
         c1 += g;
         c2 = fmaf(g, xh, c2);
@@ -241,23 +217,8 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
     }
     if (lane == 0 && dz_out) dz_out[t] = dz;
   }
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      red[wave][0][(lane + 64 * j) * 4 + i] = ag[j][i];
-      red[wave][1][(lane + 64 * j) * 4 + i] = ab[j][i];
-      red[wave][2][(lane + 64 * j) * 4 + i] = aw[j][i];
-    }
   if (lane == 0) red_b[wave] = agb;
-  __syncthreads();
-  for (int c = tid; c < 3 * d; c += LNB_THREADS) {
-    const int which = c / d, col = c - which * d;
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < LNB_WAVES; ++w) s += red[w][which][col];
-    partial[(int64_t)blockIdx.x * L + c] = s;
-  }
+  wr4_flush_cols<3, NJ, LNB_WAVES>(red, acc, d, partial + (int64_t)blockIdx.x * L);
   if (tid < 4) {
     float s = 0.f;
     if (tid == 0) {
@@ -268,61 +229,20 @@ __global__ __launch_bounds__(LNB_THREADS) void gate_ln_bwd_kernel(const float* _
   }
 }
 
-// dgamma_dbeta[c] (c < 2 d: dgamma then dbeta) = sum over the workgroups' partial rows.  A workgroup takes 32 columns (one
-// 128-byte segment of every partial row); thread (column c, slice r of 8) adds rows r, r + 8, ... in order, the eight slices meet
-// in LDS in slice order: deterministic, and the 6-MB table is read at streaming rate (the first version gave every column to one
-// thread walking all 1,024 rows: 226 us per call, 10 % of the training step).
-// Two stages (LNB_STAGE1 = 16 row groups, then one): with the whole table behind 48 workgroups the second version still took 38 us
-// per call -- 128 dependent-latency trips per thread on a fifth of the chip (profiles/r03_dispatch_kernels.md).
-constexpr int LNB_STAGE1 = 16;
-__global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float* __restrict__ partial, int n_rows, int two_d,
-                                                                   int rows_per_block, float* __restrict__ out) {
-  __shared__ float red[8][32];
-  const int c = blockIdx.x * 32 + (threadIdx.x & 31), r = threadIdx.x >> 5;
-  const int row0 = blockIdx.y * rows_per_block;
-  int row1 = row0 + rows_per_block;
-  if (row1 > n_rows) row1 = n_rows;
-  float s = 0.f;
-  if (c < two_d)
-    for (int row = row0 + r; row < row1; row += 8) s += partial[(int64_t)row * two_d + c];
-  red[r][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (r == 0 && c < two_d) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t += red[i][threadIdx.x & 31];
-    out[(int64_t)blockIdx.y * two_d + c] = t;
-  }
-}
-
-inline int lnb_grid(int64_t T) {
-  int64_t need = (T + LNB_WAVES - 1) / LNB_WAVES;
-  const int64_t cap = (int64_t)smoe_num_cus() * 4;      // 16 waves per CU: every lane keeps 2 x NJ 16-byte loads in flight
-  if (need > cap) need = cap;
-  return (int)(need < 1 ? 1 : need);
-}
+inline int lnb_grid(int64_t T) { return wr4_grid(T, LNB_WAVES, 4); }     // 16 waves per CU: every lane keeps 2 x NJ 16-byte loads in flight
 
 template <typename DYT>
 int lnb_launch(const float* x, const void* dy, const float* gamma, const float* dres, float eps, int64_t T, int d, float* dx,
                float* partial, float* dgamma_dbeta, hipStream_t s) {
   const int grid = lnb_grid(T);
-#define LNB(NJ) hipLaunchKernelGGL((layernorm_bwd_kernel<DYT, NJ>), dim3(grid), dim3(LNB_THREADS), 0, s, x, (const DYT*)dy, gamma, dres, eps, T, d, dx, partial)
   const int nj = (d / 4 + 63) / 64;
-  switch (nj) {
-    case 1: LNB(1); break;
-    case 2: LNB(2); break;
-    case 3: LNB(3); break;
-    case 4: LNB(4); break;
-    default: smoe_set_error("smoe_layernorm_bwd: d=%d out of range (d <= 1024)", d); return 1;
-  }
-#undef LNB
+  const bool ok = wr4_dispatch_nj(nj, [&](auto NJ) {
+    hipLaunchKernelGGL((layernorm_bwd_kernel<DYT, decltype(NJ)::value>), dim3(grid), dim3(LNB_THREADS), 0, s, x, (const DYT*)dy, gamma,
+                       dres, eps, T, d, dx, partial);
+  });
+  if (!ok) { smoe_set_error("smoe_layernorm_bwd: d=%d out of range (d <= 1024)", d); return 1; }
   SMOE_CHECK_LAUNCH("smoe_layernorm_bwd");
-  float* stage1 = partial + (size_t)grid * 2 * d;        // [LNB_STAGE1][2 d] behind the per-workgroup rows
-  const int rpb = (grid + LNB_STAGE1 - 1) / LNB_STAGE1;
-  hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((2 * d + 31) / 32, LNB_STAGE1), dim3(256), 0, s, partial, grid, 2 * d, rpb,
-                     stage1);
-  hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((2 * d + 31) / 32, 1), dim3(256), 0, s, stage1, LNB_STAGE1, 2 * d, LNB_STAGE1,
-                     dgamma_dbeta);
+  wr4_reduce_partials(partial, grid, 2 * d, dgamma_dbeta, 2 * d, nullptr, s);
   SMOE_CHECK_LAUNCH("smoe_layernorm_bwd/reduce");
   return 0;
 }
@@ -333,21 +253,14 @@ int glnb_launch(const float* x, const void* g_f, const float* g_out, const float
                 float* partial, float* out, hipStream_t s) {
   const int grid = lnb_grid(T);
   const int L = 3 * d + 4;
-#define GLNB(NJ) hipLaunchKernelGGL((gate_ln_bwd_kernel<GT, NJ>), dim3(grid), dim3(LNB_THREADS), 0, s, x, (const GT*)g_f, g_out, gamma, beta, eps, gate_w, gate_b, mask, gate_on, T, d, dx, dz, partial)
   const int nj = (d / 4 + 63) / 64;
-  switch (nj) {
-    case 1: GLNB(1); break;
-    case 2: GLNB(2); break;
-    case 3: GLNB(3); break;
-    case 4: GLNB(4); break;
-    default: smoe_set_error("smoe_gate_ln_bwd: d=%d out of range (d <= 1024)", d); return 1;
-  }
-#undef GLNB
+  const bool ok = wr4_dispatch_nj(nj, [&](auto NJ) {
+    hipLaunchKernelGGL((gate_ln_bwd_kernel<GT, decltype(NJ)::value>), dim3(grid), dim3(LNB_THREADS), 0, s, x, (const GT*)g_f, g_out, gamma,
+                       beta, eps, gate_w, gate_b, mask, gate_on, T, d, dx, dz, partial);
+  });
+  if (!ok) { smoe_set_error("smoe_gate_ln_bwd: d=%d out of range (d <= 1024)", d); return 1; }
   SMOE_CHECK_LAUNCH("smoe_gate_ln_bwd");
-  float* stage1 = partial + (size_t)grid * L;
-  const int rpb = (grid + LNB_STAGE1 - 1) / LNB_STAGE1;
-  hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((L + 31) / 32, LNB_STAGE1), dim3(256), 0, s, partial, grid, L, rpb, stage1);
-  hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((L + 31) / 32, 1), dim3(256), 0, s, stage1, LNB_STAGE1, L, LNB_STAGE1, out);
+  wr4_reduce_partials(partial, grid, L, out, L, nullptr, s);
   SMOE_CHECK_LAUNCH("smoe_gate_ln_bwd/reduce");
   return 0;
 }
@@ -444,7 +357,7 @@ extern "C" int smoe_gate_dgrad(const float* dl, const float* w, int64_t T, int E
 
 extern "C" size_t smoe_gate_ln_bwd_workspace_bytes(int64_t T, int d) {
   if (T < 0 || d <= 0) return 0;
-  return ((size_t)lnb_grid(T) + LNB_STAGE1) * (3 * (size_t)d + 4) * sizeof(float);
+  return ((size_t)lnb_grid(T) + WR4_STAGE1) * (3 * (size_t)d + 4) * sizeof(float);
 }
 
 // see gate_ln_bwd_kernel.  x f32 [T, d] (the half's input), g_f [T, d] (f32 / f16 / bf16), g_out f32 [T, d] or NULL, gamma / beta f32 [d]
@@ -473,7 +386,7 @@ extern "C" int smoe_gate_ln_bwd(const float* x, const void* g_f, int g_f_dtype, 
 
 extern "C" size_t smoe_layernorm_bwd_workspace_bytes(int64_t T, int d) {
   if (T < 0 || d <= 0) return 0;
-  return ((size_t)lnb_grid(T) + LNB_STAGE1) * 2 * (size_t)d * sizeof(float);
+  return ((size_t)lnb_grid(T) + WR4_STAGE1) * 2 * (size_t)d * sizeof(float);
 }
 
 extern "C" int smoe_layernorm_bwd(const float* x, const void* dy, int dy_dtype, const float* gamma, const float* dres, float eps,

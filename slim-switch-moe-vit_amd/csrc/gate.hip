@@ -94,8 +94,7 @@ __global__ __launch_bounds__(256) void zero_row_output_kernel(const float* __res
       const float gl = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
       acc = fmaf(wrow[j], gl, acc);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    acc = wave_sum(acc);
     total += (ex[r] / ssum) * (acc + (b2 ? b2[(int64_t)e * d + c] : 0.f));
   }
   if (lane == 0) out[c] = total;

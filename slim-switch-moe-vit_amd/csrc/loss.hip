@@ -161,14 +161,9 @@ struct MaxSum {
 constexpr int CE_K = 8;     // logits per thread and step
 constexpr int NW = LOSS_THREADS / 64;     // waves of a workgroup
 
-// THE sum of a value (f32, f64, int) over the workgroup, in two halves around the caller's one __syncthreads(): wave_sum over the
-// wave, lane 0 of each wave stores it to red[wave], the barrier, then tree4(red) = (w0 + w1) + (w2 + w3) on whoever needs it.
-// Neither half synchronises: a kernel that reduces several values stores them all and synchronises once.
-template <typename V> __device__ __forceinline__ V wave_sum(V v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+// THE sum of a value (f32, f64, int) over the workgroup, in two halves around the caller's one __syncthreads(): wave_sum
+// (smoe_common.h) over the wave, lane 0 of each wave stores it to red[wave], the barrier, then tree4(red) = (w0 + w1) + (w2 + w3) on
+// whoever needs it.  Neither half synchronises: a kernel that reduces several values stores them all and synchronises once.
 template <typename V> __device__ __forceinline__ V tree4(const V (&red)[NW]) { return (red[0] + red[1]) + (red[2] + red[3]); }
 // ... and MaxSum's second half, over the waves' (m, s) as they lie in LDS: the same pairing, (w0, w1), (w2, w3), then the two
 __device__ __forceinline__ MaxSum tree4(const float (&rm)[NW], const float (&rs)[NW]) {

@@ -33,12 +33,6 @@ __device__ __forceinline__ double ng_noisy(const float* __restrict__ l, const fl
   return training ? fma(ep ? (double)ep[e] : 0.0, ng_sigma(l[E + e]), c) : c;
 }
 
-__device__ __forceinline__ double ng_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // ---- forward, row pass ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NG_THREADS) void noisy_gate_rows_kernel(const float* __restrict__ logits2, const float* __restrict__ eps,
                                                                      int64_t T, int E, int k, int training, int64_t* __restrict__ idx,
@@ -117,8 +111,8 @@ __global__ __launch_bounds__(NG_THREADS) void noisy_gate_rows_kernel(const float
         cl = 0.5 * (1.0 + erf((c - thr) / sg * 0.70710678118654752440));
       }
     }
-    ci = ng_wave_sum(ci);
-    cl = ng_wave_sum(cl);
+    ci = wave_sum(ci);
+    cl = wave_sum(cl);
     if (lane == 0) {
       red[wave][e] = ci;
       red[wave][E + e] = cl;

@@ -48,8 +48,7 @@ __device__ __forceinline__ void sumsq_block(const GT* __restrict__ g, int64_t n,
       }
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   if (__ballot(bad) && (threadIdx.x & 63) == 0 && found_inf) *found_inf = 1.0f;
   __syncthreads();

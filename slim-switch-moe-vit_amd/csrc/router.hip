@@ -93,8 +93,7 @@ __global__ __launch_bounds__(ROUTER_THREADS, (MODE == 0 ? 4 : 2)) void router_ke
     float s = 0.f;
     if (e < E)
       for (int c = lane; c < d; c += 64) { const float w = wg[(size_t)e * d + c]; s = fmaf(w, w, s); }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    s = wave_sum(s);
     if (lane == 0) lds_wn2[e] = s;
   }
   __syncthreads();
@@ -240,8 +239,7 @@ __global__ __launch_bounds__(ROUTER_THREADS, (MODE == 0 ? 4 : 2)) void router_ke
       for (int c = 0; c < NCH; ++c)
 #pragma unroll
         for (int j = 0; j < 4; ++j) xs = fmaf(xc[c][j], xc[c][j], xs);
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) xs += __shfl_xor(xs, m, 64);
+      xs = wave_sum(xs);
       logits_f32();
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes precede its reads
       __builtin_amdgcn_wave_barrier();
@@ -287,8 +285,7 @@ __global__ __launch_bounds__(ROUTER_THREADS, (MODE == 0 ? 4 : 2)) void router_ke
       const float mx = chosen_val[0];
       float s = 0.f;
       for (int e = lane; e < E; e += 64) s += expf(my_logit[e] - mx);
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+      s = wave_sum(s);
       if (probs_out) {
         for (int e = lane; e < E; e += 64) probs_out[t * (int64_t)E + e] = expf(my_logit[e] - mx) / s;
       }

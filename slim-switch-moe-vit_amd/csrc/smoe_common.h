@@ -146,6 +146,13 @@ __device__ __forceinline__ void list_push(int32_t* count, int32_t* list, int64_t
   if (slot >= 0 && (int64_t)slot < cap) list[slot] = (int32_t)t;
 }
 
+// THE sum of a value (f32, f64, int) over the 64 lanes of a wave, the same in every lane: the xor butterfly, m = 32 .. 1
+template <typename V> __device__ __forceinline__ V wave_sum(V v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
 // ---- LayerNorm of one row held by ONE WAVE -----------------------------------------------------------------------------------
 // Lane l holds v[i][0..8) = the row's elements [8 l + 512 i, 8 l + 512 i + 8) (zeros past d).  THE arithmetic of every wave-per-row
 // LayerNorm of the library -- smoe_layernorm / smoe_embed_ln / smoe_layernorm_rows at d >= 768, smoe_gather_combine_ln at every d --
@@ -158,9 +165,7 @@ __device__ __forceinline__ void wave_row_stats(const float (&v)[NI][8], int d, i
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int q = 0; q < 8; ++q) s1 += v[i][q];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s1 += __shfl_xor(s1, m, 64);
-  mean = s1 * inv_d;
+  mean = wave_sum(s1) * inv_d;
   float s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < NI; ++i)
@@ -168,9 +173,7 @@ __device__ __forceinline__ void wave_row_stats(const float (&v)[NI][8], int d, i
 #pragma unroll
       for (int q = 0; q < 8; ++q) { const float dv = v[i][q] - mean; s2 = fmaf(dv, dv, s2); }
     }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
-  rstd = rsqrtf(s2 * inv_d + eps);
+  rstd = rsqrtf(wave_sum(s2) * inv_d + eps);
 }
 
 // ... and the affine output of one element.  The f32 value is the result: the empty asm keeps the compiler from fusing the FMA with a

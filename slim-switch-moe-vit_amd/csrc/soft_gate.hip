@@ -2,28 +2,22 @@
 // and their straight-through estimator by the relaxation skip_tk = 1 - p, tk = p), forward, fused with the LayerNorm in front of it:
 //     xn = LN(x) gamma + beta (or x),  z = <xn, w> + b,  p = sigmoid(z),  tk = xn p,  mask = (1 - p, p)
 // ONE pass over x writes the residual image xn32, the operator's input tk as a 16-bit image (attention half) or an f32 image (the MoE
-// half's router and scatter) and the mask.  Nothing is decided here, so there is no f64 redo: the layout is gate_ln_bwd_kernel's
-// (dense_bwd.hip) -- one wave per row, 16-byte loads per lane, a grid-stride loop under a grid cap, 64-bit row offsets -- and the
-// LayerNorm / logit arithmetic is that kernel's operation for operation, so the backward recomputes THIS pass's xn and z bit for bit.
-// At d = 192 a row is 48 sixteen-byte chunks: 16 lanes of the wave idle, as in gate_ln_bwd_kernel.
+// half's router and scatter) and the mask.  Nothing is decided here, so there is no f64 redo: the layout is wave_row4.h's --
+// one wave per row, 16-byte loads per lane, a grid-stride loop under a grid cap, 64-bit row offsets -- and the LayerNorm / logit
+// arithmetic is that header's (wr4_row_stats and the xhat / xn expressions it states) with gate_ln_bwd_kernel's logit sum
+// (dense_bwd.hip), so the backward recomputes THIS pass's xn and z bit for bit.  At d = 192 a row is 48 sixteen-byte chunks: 16
+// lanes of the wave idle.
 // Bound: HBM (4 T d bytes read, 4 T d + 2 T d or 4 T d written).
 // Skip counter (Gate._skipped_tokens): every wave adds 1 - p of its rows in double, the four waves of a workgroup meet in LDS in wave
 // order, every workgroup writes ONE partial sum; a second, one-wave launch adds the partial sums in double in a fixed order (lane l:
 // l, l + 64, ... in index order; the lanes in a fixed tree), rounds with rint and adds to the int32 counter.  No atomics, no host
 // access.  A row whose 1 - p is NaN (a NaN / inf row) counts as 0: it never poisons the other rows' count.
-#include "smoe_common.h"
-#include <type_traits>
+#include "wave_row4.h"
 
 namespace {
 
 constexpr int SG_THREADS = 256;
 constexpr int SG_WAVES = SG_THREADS / 64;
-
-__device__ __forceinline__ float sg_wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 template <typename NT> __device__ __forceinline__ void sg_store4_16(NT* dst, const f32x4& v) {   // smoe_gate_ln_router's xn16 conversion
   if constexpr (std::is_same<NT, f16>::value) {
@@ -62,26 +56,10 @@ __global__ __launch_bounds__(SG_THREADS) void soft_gate_ln_fwd_kernel(const floa
   for (int64_t t = row0; t < T; t += stride) {
     const int64_t rowoff = t * (int64_t)d;
     float xv[NJ][4];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int c = lane + 64 * j;
-      if (c < nchunk) load4(x + rowoff + c * 4, xv[j]);
-      else xv[j][0] = xv[j][1] = xv[j][2] = xv[j][3] = 0.f;
-    }
-    if constexpr (LN) {   // two passes in registers, gate_ln_bwd_kernel's sums in its order
-      float s1 = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) s1 += (xv[j][0] + xv[j][1]) + (xv[j][2] + xv[j][3]);
-      const float mean = sg_wave_sum(s1) * inv_d;
-      float s2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if (lane + 64 * j < nchunk) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { const float dv = xv[j][i] - mean; s2 = fmaf(dv, dv, s2); }
-        }
-      }
-      const float rstd = rsqrtf(sg_wave_sum(s2) * inv_d + eps);
+    wr4_load(nchunk, lane, wr4_row(x + rowoff, xv));
+    if constexpr (LN) {   // xv becomes xn, by the steps gate_ln_bwd_kernel recomputes it with
+      float mean, rstd;
+      wr4_row_stats<false, NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const bool in = lane + 64 * j < nchunk;
@@ -94,7 +72,7 @@ __global__ __launch_bounds__(SG_THREADS) void soft_gate_ln_fwd_kernel(const floa
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int i = 0; i < 4; ++i) az = fmaf(xv[j][i], wv[j][i], az);
-    const float z = sg_wave_sum(az) + bias;
+    const float z = wave_sum(az) + bias;
     // p and 1 - p each as ONE division by 1 + e, e = exp(-|z|): neither is a difference from a rounded value (1 - p taken from the
     // rounded p loses about |z| log2(e) bits once the gate saturates; the e / (1 + e)^2 comment of skip_gate_bwd_kernel)
     const float e = expf(-fabsf(z));
@@ -139,33 +117,23 @@ __global__ __launch_bounds__(64) void soft_gate_count_kernel(const double* __res
   const int lane = threadIdx.x;
   double s = 0.0;
   for (int i = lane; i < n; i += 64) s += partial[i];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+  s = wave_sum(s);
   if (lane == 0) *counter += (int32_t)rint(s);
 }
 
-inline int sg_grid(int64_t T) {
-  int64_t need = (T + SG_WAVES - 1) / SG_WAVES;
-  const int64_t cap = (int64_t)smoe_num_cus() * 4;      // 16 waves per CU, as the backward pass (lnb_grid)
-  if (need > cap) need = cap;
-  return (int)(need < 1 ? 1 : need);
-}
+inline int sg_grid(int64_t T) { return wr4_grid(T, SG_WAVES, 4); }     // 16 waves per CU, as the backward pass (dense_bwd.hip lnb_grid)
 
 struct SoftGateArgs {
   const float* x; const float* gamma; const float* beta; float eps; const float* gate_w; const float* gate_b;
   int64_t T; int d; float* xn32; void* tk16; float* tk32; float* mask; double* partial; int grid; hipStream_t s;
 };
 
-template <typename NT, bool LN> int sg_launch(const SoftGateArgs& a) {
-#define SGF(NJ) hipLaunchKernelGGL((soft_gate_ln_fwd_kernel<NT, NJ, LN>), dim3(a.grid), dim3(SG_THREADS), 0, a.s, a.x, a.gamma, a.beta, a.eps, a.gate_w, a.gate_b, a.T, a.d, a.xn32, (NT*)a.tk16, a.tk32, a.mask, a.partial)
-  switch (a.d) {
-    case 192: SGF(1); break;
-    case 384: SGF(2); break;
-    case 768: SGF(3); break;
-    case 1024: SGF(4); break;
-    default: smoe_set_error("smoe_soft_gate_ln_fwd: unsupported d=%d", a.d); return 1;
-  }
-#undef SGF
+template <typename NT, bool LN> int sg_launch(const SoftGateArgs& a) {   // (a.d is one of the four supported widths)
+  const bool ok = wr4_dispatch_nj((a.d / 4 + 63) / 64, [&](auto nj) {
+    hipLaunchKernelGGL((soft_gate_ln_fwd_kernel<NT, decltype(nj)::value, LN>), dim3(a.grid), dim3(SG_THREADS), 0, a.s, a.x, a.gamma,
+                       a.beta, a.eps, a.gate_w, a.gate_b, a.T, a.d, a.xn32, (NT*)a.tk16, a.tk32, a.mask, a.partial);
+  });
+  if (!ok) { smoe_set_error("smoe_soft_gate_ln_fwd: unsupported d=%d", a.d); return 1; }
   SMOE_CHECK_LAUNCH("smoe_soft_gate_ln_fwd");
   return 0;
 }

@@ -4,18 +4,18 @@
 //     bucket b = the given one, or argmin_k sum_j (x_j - c_kj)^2 over the RAW row (first minimum; a NaN distance counts as the
 //                smallest and the first NaN wins: torch.argmin);
 //     y = xhat weights[b] + biases[b].
-// Forward: ONE launch, one wave per row (a row of d <= 1024 floats = up to 16 per lane, the layout of layernorm_bwd_kernel), the
+// Forward: ONE launch, one wave per row (a row of d <= 1024 floats = up to 16 per lane: the layout of wave_row4.h), the
 // statistics two-pass in registers.  The K distances are accumulated in DOUBLE in the direct form: upstream's f32 expanded form
 // |x|^2 + |c|^2 - 2 x.c misassigns rows near a bisector, the f64 direct form is the float64 evaluation itself up to summation order
 // (relative error ~ d 2^-53).  K d f64 FMAs per row on a full-rate f64 pipe.  The centroids are always staged in LDS: up to 48 KB
 // with four waves per workgroup and several workgroups per CU, above that (to 128 KB) with one 16-wave workgroup per CU.
 // The K per-lane sums meet across the wave by halving (K - 1 + 6 - log2 K double shuffles instead of 6 K), in a fixed order.
-// Backward: dx as layernorm_bwd_kernel (statistics recomputed from x, gamma = weights[b] per row) in one launch that also leaves
-// the row statistics; the per-bucket sums dweights[k] = sum_{rows of k} dy xhat, dbiases[k] = sum dy in a second launch where a
+// Backward: dx in the form wave_row4.h states (statistics recomputed from x, gamma = weights[b] per row) in one launch that also
+// leaves the row statistics; the per-bucket sums dweights[k] = sum_{rows of k} dy xhat, dbiases[k] = sum dy in a second launch where a
 // thread owns a COLUMN and walks rows -- its K x 2 accumulators live in LDS (a register array indexed by the bucket would go to
 // scratch), every workgroup writes one partial table, two reduce launches add them in workgroup order: no atomics, the same bits
 // run to run, and the rows of an empty bucket are sums of nothing = exact zeros.
-#include "smoe_common.h"
+#include "wave_row4.h"
 #include <math.h>
 
 namespace {
@@ -25,42 +25,6 @@ constexpr int SLN_WAVES = SLN_THREADS / 64;
 constexpr int SLN_BIG_THREADS = 1024;     // the forward's workgroup when the centroid table leaves room for one workgroup per CU
 constexpr int SLN_LDS_FLOATS = 12288;      // a centroid table of up to K * d = this (48 KB) runs SLN_THREADS-wide workgroups, several per CU
 constexpr int SLN_MAX_K = 32;
-constexpr int SLN_STAGE1 = 16;
-
-__device__ __forceinline__ float sln_wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// Two-pass statistics of the row a wave holds, about a PIVOT (the row's first element): xv becomes x - pivot (exact, or rounded at
-// the size of the row's spread), mean = mean(x - pivot), rstd = rsqrt(var + eps).  A common offset of the row (x = 300 + noise) costs
-// the mean nothing: an f32 sum of the raw values would carry the offset's rounding (ulp(300 d) / d per row) into every x - mean.
-// Returns the pivot.
-template <int NJ>
-__device__ __forceinline__ float sln_row_stats(float (&xv)[NJ][4], int nchunk, int lane, float inv_d, float eps, float& mean,
-                                               float& rstd) {
-  const float pivot = __shfl(xv[0][0], 0, 64);
-  float s1 = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const bool in = lane + 64 * j < nchunk;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xv[j][i] = in ? xv[j][i] - pivot : 0.f;
-    s1 += (xv[j][0] + xv[j][1]) + (xv[j][2] + xv[j][3]);
-  }
-  mean = sln_wave_sum(s1) * inv_d;
-  float s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    if (lane + 64 * j < nchunk) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const float dv = xv[j][i] - mean; s2 = fmaf(dv, dv, s2); }
-    }
-  }
-  rstd = rsqrtf(sln_wave_sum(s2) * inv_d + eps);
-  return pivot;
-}
 
 // torch.argmin's order on (distance, index): a NaN beats every number, among equals (or two NaNs) the smaller index wins
 __device__ __forceinline__ bool sln_better(double a, int ka, double b, int kb) {
@@ -131,7 +95,7 @@ __global__ __launch_bounds__(THREADS) void switch_ln_fwd_kernel(const float* __r
   for (int64_t t = row0; t < T; t += stride) {
     float xv[NJ][4];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < NJ; ++j) {     // (its own row load: through wr4_load the kernel took 2 - 4 more VGPRs)
       const int c = lane + 64 * j;
       if (c < nchunk) {
         load4(x + t * (int64_t)d + c * 4, xv[j]);
@@ -167,7 +131,7 @@ __global__ __launch_bounds__(THREADS) void switch_ln_fwd_kernel(const float* __r
     }
     const bool in_range = b >= 0 && b < (int64_t)K;
     float mean, rstd;
-    sln_row_stats<NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
+    wr4_row_stats<true, NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = lane + 64 * j;
@@ -191,7 +155,7 @@ __global__ __launch_bounds__(THREADS) void switch_ln_fwd_kernel(const float* __r
   }
 }
 
-// dx[t] = rstd (g - mean(g) - xhat mean(g xhat)),  g = dy weights[b_t]  (weights null: g = dy);  stats[t] = (pivot, mean - pivot, rstd, -): the row statistics of sln_row_stats.
+// dx[t] = rstd (g - mean(g) - xhat mean(g xhat)),  g = dy weights[b_t]  (weights null: g = dy);  stats[t] = (pivot, mean - pivot, rstd, -): the row statistics of wr4_row_stats<true>.
 // A bucket outside [0, K) reads nothing from the table and gives a NaN row.
 template <typename DYT, int NJ>
 __global__ __launch_bounds__(SLN_THREADS) void switch_ln_bwd_dx_kernel(const float* __restrict__ x, const DYT* __restrict__ dy,
@@ -208,6 +172,8 @@ __global__ __launch_bounds__(SLN_THREADS) void switch_ln_bwd_dx_kernel(const flo
     const int64_t b = buckets[t];
     const bool in_range = b >= 0 && b < (int64_t)K;
     float xv[NJ][4], gv[NJ][4];
+    // its own row load: g = dy weights[b] under the chunk's one bounds test (behind wr4_load the product lives twice across the
+    // multiply's branch: 12 - 16 more VGPRs; profiles/wave_row4_ab.md)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = lane + 64 * j;
@@ -225,7 +191,7 @@ __global__ __launch_bounds__(SLN_THREADS) void switch_ln_bwd_dx_kernel(const flo
       }
     }
     float mean, rstd;
-    const float pivot = sln_row_stats<NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
+    const float pivot = wr4_row_stats<true, NJ>(xv, nchunk, lane, inv_d, eps, mean, rstd);
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -237,8 +203,8 @@ __global__ __launch_bounds__(SLN_THREADS) void switch_ln_bwd_dx_kernel(const flo
         xv[j][i] = xh;
       }
     }
-    c1 = sln_wave_sum(c1) * inv_d;
-    c2 = sln_wave_sum(c2) * inv_d;
+    c1 = wave_sum(c1) * inv_d;
+    c2 = wave_sum(c2) * inv_d;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = lane + 64 * j;
@@ -306,38 +272,6 @@ __global__ __launch_bounds__(SLN_THREADS) void switch_ln_bwd_cols_kernel(const f
   }
 }
 
-// out[blockIdx.y][c] (c < L) = sum over the partial rows [blockIdx.y * rows_per_block, +rows_per_block) in row order; thread
-// (column c, slice r of 8) adds rows r, r + 8, ..., the eight slices meet in LDS in slice order (layernorm_bwd_reduce_kernel's
-// scheme).  Columns from `split` on go to out_b (the last stage writes dweights and dbiases apart).
-__global__ __launch_bounds__(256) void switch_ln_reduce_kernel(const float* __restrict__ partial, int n_rows, int L,
-                                                               int rows_per_block, float* __restrict__ out_a, int split,
-                                                               float* __restrict__ out_b) {
-  __shared__ float red[8][32];
-  const int c = blockIdx.x * 32 + (threadIdx.x & 31), r = threadIdx.x >> 5;
-  const int row0 = blockIdx.y * rows_per_block;
-  int row1 = row0 + rows_per_block;
-  if (row1 > n_rows) row1 = n_rows;
-  float s = 0.f;
-  if (c < L)
-    for (int row = row0 + r; row < row1; row += 8) s += partial[(int64_t)row * L + c];
-  red[r][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (r == 0 && c < L) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t += red[i][threadIdx.x & 31];
-    if (c < split) out_a[(int64_t)blockIdx.y * L + c] = t;
-    else out_b[c - split] = t;
-  }
-}
-
-inline int sln_grid(int64_t T, int per_cu) {
-  int64_t need = (T + SLN_WAVES - 1) / SLN_WAVES;
-  const int64_t cap = (int64_t)smoe_num_cus() * per_cu;
-  if (need > cap) need = cap;
-  return (int)(need < 1 ? 1 : need);
-}
-
 // row slabs of the column pass: 16 rows at least per slab, at most 4 workgroups per CU over all column tiles
 inline int sln_slabs(int64_t T, int d) {
   const int tiles = (d + SLN_THREADS - 1) / SLN_THREADS;
@@ -392,15 +326,12 @@ int sln_bwd_launch(const float* x, const void* dyv, const float* weights, const 
   const DYT* dy = (const DYT*)dyv;
   float* stats = ws;
   float* partial = ws + sln_stats_floats(T);
-  const int grid = sln_grid(T, 4);
-#define SLN_B(NJ) hipLaunchKernelGGL((switch_ln_bwd_dx_kernel<DYT, NJ>), dim3(grid), dim3(SLN_THREADS), 0, s, x, dy, weights, buckets, eps, T, d, K, dx, stats)
-  switch ((d / 4 + 63) / 64) {
-    case 1: SLN_B(1); break;
-    case 2: SLN_B(2); break;
-    case 3: SLN_B(3); break;
-    default: SLN_B(4); break;
-  }
-#undef SLN_B
+  const int grid = wr4_grid(T, SLN_WAVES, 4);
+  const bool ok = wr4_dispatch_nj((d / 4 + 63) / 64, [&](auto nj) {
+    hipLaunchKernelGGL((switch_ln_bwd_dx_kernel<DYT, decltype(nj)::value>), dim3(grid), dim3(SLN_THREADS), 0, s, x, dy, weights, buckets,
+                       eps, T, d, K, dx, stats);
+  });
+  if (!ok) { smoe_set_error("smoe_switch_ln_bwd: d=%d out of range (d <= 1024)", d); return 1; }
   SMOE_CHECK_LAUNCH("smoe_switch_ln_bwd/dx");
   if (!dweights) return 0;
   const int slabs = sln_slabs(T, d), tiles = (d + SLN_THREADS - 1) / SLN_THREADS;
@@ -409,12 +340,7 @@ int sln_bwd_launch(const float* x, const void* dyv, const float* weights, const 
   hipLaunchKernelGGL((switch_ln_bwd_cols_kernel<DYT>), dim3(tiles, slabs), dim3(SLN_THREADS), (size_t)K * 2 * SLN_THREADS * sizeof(float),
                      s, x, dy, buckets, stats, T, d, K, rows_per_slab, partial);
   SMOE_CHECK_LAUNCH("smoe_switch_ln_bwd/cols");
-  float* stage1 = partial + (size_t)slabs * L;
-  const int rpb = (slabs + SLN_STAGE1 - 1) / SLN_STAGE1;
-  hipLaunchKernelGGL(switch_ln_reduce_kernel, dim3((L + 31) / 32, SLN_STAGE1), dim3(256), 0, s, partial, slabs, L, rpb, stage1, L,
-                     (float*)nullptr);
-  hipLaunchKernelGGL(switch_ln_reduce_kernel, dim3((L + 31) / 32, 1), dim3(256), 0, s, stage1, SLN_STAGE1, L, SLN_STAGE1, dweights,
-                     K * d, dbiases);
+  wr4_reduce_partials(partial, slabs, L, dweights, K * d, dbiases, s);     // the last stage writes dweights and dbiases apart
   SMOE_CHECK_LAUNCH("smoe_switch_ln_bwd/reduce");
   return 0;
 }
@@ -442,22 +368,15 @@ extern "C" int smoe_switch_ln_fwd(const float* x, const float* weights, const fl
   int kp = 0;
   if (select) { kp = 2; while (kp < K) kp *= 2; }
   const bool big = select && K * d > SLN_LDS_FLOATS;
-  int grid = sln_grid(T, 8);
-  if (big) {                                  // one workgroup of 16 waves per CU
-    const int64_t need = (T + SLN_BIG_THREADS / 64 - 1) / (SLN_BIG_THREADS / 64);
-    grid = (int)(need < smoe_num_cus() ? need : smoe_num_cus());
-  }
+  // several SLN_THREADS-wide workgroups per CU, or one workgroup of 16 waves per CU
+  const int grid = big ? wr4_grid(T, SLN_BIG_THREADS / 64, 1) : wr4_grid(T, SLN_WAVES, 8);
   hipStream_t s = (hipStream_t)stream;
   const float* cent = select ? centroids : nullptr;
   int rc = 0;
-#define SLN_NJ(NJ) sln_fwd_kp<NJ>(kp, big, grid, s, x, weights, biases, cent, buckets_in, bucket_all, eps, T, d, K, y, buckets_out)
-  switch ((d / 4 + 63) / 64) {
-    case 1: rc = SLN_NJ(1); break;
-    case 2: rc = SLN_NJ(2); break;
-    case 3: rc = SLN_NJ(3); break;
-    default: rc = SLN_NJ(4); break;
-  }
-#undef SLN_NJ
+  const bool ok = wr4_dispatch_nj((d / 4 + 63) / 64, [&](auto nj) {
+    rc = sln_fwd_kp<decltype(nj)::value>(kp, big, grid, s, x, weights, biases, cent, buckets_in, bucket_all, eps, T, d, K, y, buckets_out);
+  });
+  if (!ok) { smoe_set_error("smoe_switch_ln_fwd: d=%d out of range (d <= 1024)", d); return 1; }
   if (rc != 0) return rc;
   SMOE_CHECK_LAUNCH("smoe_switch_ln_fwd");
   return 0;
@@ -465,7 +384,7 @@ extern "C" int smoe_switch_ln_fwd(const float* x, const float* weights, const fl
 
 extern "C" size_t smoe_switch_ln_bwd_workspace_bytes(int64_t T, int d, int K) {
   if (T < 0 || !sln_shape_ok(d, K)) return 0;
-  return (sln_stats_floats(T) + ((size_t)sln_slabs(T, d) + SLN_STAGE1) * 2 * (size_t)K * d) * sizeof(float);
+  return (sln_stats_floats(T) + ((size_t)sln_slabs(T, d) + WR4_STAGE1) * 2 * (size_t)K * d) * sizeof(float);
 }
 
 extern "C" int smoe_switch_ln_bwd(const float* x, const void* dy, int dy_dtype, const float* weights, const int64_t* buckets,

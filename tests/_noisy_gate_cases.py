@@ -193,7 +193,7 @@ def _sigma32(raw):
 
 
 def _wave_sum(rows):
-    """[64, C] -> [C]: the xor butterfly of ng_wave_sum (lane 0's value)"""
+    """[64, C] -> [C]: the xor butterfly of wave_sum (lane 0's value)"""
     lanes = torch.arange(64)
     for m in (32, 16, 8, 4, 2, 1):
         rows = rows + rows[lanes ^ m]

@@ -110,7 +110,7 @@ PLAN_FUSED_E, PLAN_THREADS, PLAN_CH = 64, 256, 1024      # csrc/dispatch.hip
 
 
 def ln_nj(d: int) -> int:
-    """dense_bwd.hip lnb_launch / glnb_launch: 64 lanes x 4 columns per register chunk"""
+    """dense_bwd.hip lnb_launch / glnb_launch (wave_row4.h wr4_dispatch_nj): 64 lanes x 4 columns per register chunk"""
     return (d // 4 + 63) // 64
 
 

@@ -55,6 +55,24 @@ def test_layernorm_backward_matches_float64_autograd(d, dy_dt):
     assert _rel(ln.weight.grad, wr.grad) <= 2e-3
 
 
+@pytest.mark.parametrize("d", [4, 260, 1024])
+@pytest.mark.parametrize("T", [1, 5, 67])
+@pytest.mark.parametrize("g_dt", [torch.float32, torch.float16])
+def test_gate_ln_backward_with_its_gate_off_is_the_layernorm_backward_bit_for_bit(d, T, g_dt):
+    """gate_ln_bwd_kernel and layernorm_bwd_kernel run the same statistics and column-sum flush (csrc/wave_row4.h) and the dx tail in
+    the one form that header states, and with the gate off dz = 0, so dxn = fmaf(g, 1, fmaf(0, w, 0)) = g: dx, dgamma and dbeta of the
+    two launches are the same bits.  d = one chunk, one chunk into the second 256-column slab, four full slabs; T = 1, 2 and 17 partial rows."""
+    g = _gen(1000 * d + T)
+    x = (torch.randn(T, d, generator=g) * 2 + 0.5).to(DEV)
+    gy = torch.randn(T, d, generator=g).to(g_dt).to(DEV)
+    ln_w, ln_b = (1 + 0.3 * torch.randn(d, generator=g)).to(DEV), (0.2 * torch.randn(d, generator=g)).to(DEV)
+    gate_w, gate_b = (torch.randn(d, generator=g) * d ** -0.5).to(DEV), torch.randn(1, generator=g).to(DEV)
+    dx, dln_w, dln_b, _, _, _ = ops.gate_ln_bwd(x, gy, None, ln_w, ln_b, 1e-6, gate_w, gate_b, None, gate_on=False)
+    rx, rw, rb = ops.layernorm_bwd(x, gy, ln_w, 1e-6)
+    assert bool(torch.isfinite(rx).all()) and bool(torch.isfinite(rw).all()) and bool(torch.isfinite(rb).all())
+    assert torch.equal(dx, rx) and torch.equal(dln_w, rw) and torch.equal(dln_b, rb)
+
+
 @pytest.mark.parametrize("M,K,N,res", [(788, 192, 576, False), (1576, 768, 2304, False), (1000, 768, 768, True), (300, 3072, 768, False)])
 def test_linear_function_forward_and_backward_on_own_gemms(M, K, N, res):
     g = _gen(M + N)
