@@ -601,14 +601,17 @@ int smoe_layernorm_bwd(const float* x, const void* dy, int dy_dtype, const float
  * smoe_adamw_step : torch.optim.AdamW arithmetic on f32 p / m / v with the gradient g (f32 / f16 / bf16) multiplied by
  *                   *grad_mult (NULL = 1: e.g. inv_scale x clip coefficient): p *= 1 - lr wd; m = lerp(m, g, 1 - b1);
  *                   v = b2 v + (1 - b2) g^2; p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps), t = *step
- *                   (device f32, already advanced); the whole update is skipped when *found_inf != 0 (found_inf may be NULL)
+ *                   (device f32, already advanced); the whole update is skipped when *found_inf != 0 (found_inf may be NULL).
+ *                   beta1 / beta2 are DOUBLES (ABI 30): 1 - b1, 1 - b2, 1 - b1^t and sqrt(1 - b2^t) are taken in double on the
+ *                   device and rounded once -- in f32, 1.0f - 0.999f is off by 1.3e-5 of itself on every element of every update;
+ *                   lerp is torch's (g - b1 (g - m) where 1 - b1 >= 0.5, so beta1 = 0 gives m = g exactly)
  * smoe_amp_update : GradScaler.update(): found_inf ? (scale *= backoff, tracker = 0)
  *                                                 : (++tracker == interval ? (scale *= growth, tracker = 0) : -)
  * smoe_step_advance: *step += 1 unless *found_inf != 0                                                                  */
 int64_t smoe_grad_sumsq_blocks(int64_t n);
 int smoe_grad_sumsq(const void* g, int g_dtype, int64_t n, const float* inv_scale, float* partial, float* found_inf,
                     void* stream);
-int smoe_adamw_step(float* p, const void* g, int g_dtype, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+int smoe_adamw_step(float* p, const void* g, int g_dtype, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
                     float eps, float weight_decay, const float* step, const float* grad_mult, const float* found_inf,
                     void* stream);
 /* Multi-tensor forms of the two passes: ONE launch for every gradient / parameter of the step (torch's `foreach` / fused
@@ -622,7 +625,7 @@ int smoe_adamw_step(float* p, const void* g, int g_dtype, float* m, float* v, in
 int smoe_grad_sumsq_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, int g_dtype,
                           const float* inv_scale, float* partial, float* found_inf, void* stream);
 int smoe_adamw_step_multi(const int64_t* tab, const float* hyp, int n_tensors, const int32_t* blk, int64_t n_blocks,
-                          int g_dtype, float beta1, float beta2, float eps, const float* step, const float* grad_mult,
+                          int g_dtype, double beta1, double beta2, float eps, const float* step, const float* grad_mult,
                           const float* found_inf, const int64_t* shadow, void* stream);
 int smoe_amp_update(float* scale, float* growth_tracker, const float* found_inf, float growth_factor, float backoff_factor,
                     int growth_interval, void* stream);

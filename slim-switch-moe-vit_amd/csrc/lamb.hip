@@ -21,24 +21,6 @@ namespace {
 constexpr int LAMB_THREADS = 256;
 constexpr int LAMB_BLOCK = 16384;   // elements per workgroup: optim.hip's SUMSQ_BLOCK (optim._block_table builds blk for both)
 
-// b^t for the whole number t the step counter holds, in double: 1 - 0.999^1 taken in f32 is already off by 3e-5
-__device__ __forceinline__ double pow_whole(double b, float t) {
-  unsigned n = t > 0.f ? (unsigned)t : 0u;
-  double r = 1.0;
-  while (n) {
-    if (n & 1u) r *= b;
-    b *= b;
-    n >>= 1;
-  }
-  return r;
-}
-
-// bc1 = 1 - beta1^t and sqrt(bc2) = sqrt(1 - beta2^t); both 1 without bias correction
-__device__ __forceinline__ void lamb_bias(double b1, double b2, float t, int bias_correction, float& bc1, float& bc2_sqrt) {
-  bc1 = bias_correction ? (float)(1.0 - pow_whole(b1, t)) : 1.0f;
-  bc2_sqrt = bias_correction ? (float)sqrt(1.0 - pow_whole(b2, t)) : 1.0f;
-}
-
 // THE update of one element before the trust ratio: stage 1 sums its square, stage 2 applies it -- one function, so the same bits
 __device__ __forceinline__ float lamb_update(float p, float m, float v, float bc1, float bc2_sqrt, float eps, float wd) {
   const float u = (m / bc1) / (sqrtf(v) / bc2_sqrt + eps);
@@ -99,7 +81,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage1_multi_kernel(const i
   const float b1 = (float)b1d, b2 = (float)b2d, one_minus_b2 = (float)(1.0 - b2d);   // (1.0f - 0.999f is off by 1.3e-5 of itself)
   const float gm = (grad_mult ? *grad_mult : 1.0f) / (clip ? *clip : 1.0f);
   float bc1, bc2_sqrt;
-  lamb_bias(b1d, b2d, *step, bias_correction, bc1, bc2_sqrt);   // *step: already advanced for this update
+  adam_bias(b1d, b2d, *step, bias_correction, bc1, bc2_sqrt);   // *step: already advanced for this update
   float pp = 0.f, uu = 0.f;
   for (int64_t i = base + threadIdx.x * 4; i < end; i += LAMB_THREADS * 4) {
     if (i + 4 <= n) {
@@ -204,7 +186,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage2_multi_kernel(const i
   void* sh = shadow ? reinterpret_cast<void*>(shadow[t]) : nullptr;
   const int sh_dtype = shadow ? (int)shadow[(int64_t)n_t + t] : SMOE_F16;
   float bc1, bc2_sqrt;
-  lamb_bias(b1d, b2d, *step, bias_correction, bc1, bc2_sqrt);
+  adam_bias(b1d, b2d, *step, bias_correction, bc1, bc2_sqrt);
   for (int64_t i = base + threadIdx.x * 4; i < end; i += LAMB_THREADS * 4) {
     if (i + 4 <= n) {
       f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);

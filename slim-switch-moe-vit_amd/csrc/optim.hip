@@ -77,15 +77,25 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_sumsq_multi_kernel(const int
                   inv_scale ? *inv_scale : 1.0f, partial + blockIdx.x, found_inf);
 }
 
+// torch's lerp(m, g, w = 1 - beta1): m + w (g - m) for w < 0.5, g - (1 - w) (g - m) otherwise
+__device__ __forceinline__ float adamw_lerp(float m, float g, float w, float one_minus_w, bool low) {
+  const float d = g - m;
+  return low ? fmaf(w, d, m) : fmaf(-one_minus_w, d, g);
+}
+
 // elements [begin, end) of one parameter, `stride` apart per pass (begin = this thread's first element, a multiple of 4)
 // sh (optional): a 16-bit image of the parameter (the MFMA operand copy the forward reads), refreshed in the same pass -- the step
 // then needs no separate f32 -> 16-bit cast of every weight (4 bytes read + 2 written per element) before the next forward
 template <typename GT>
 __device__ __forceinline__ void adamw_range(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, int64_t begin, int64_t end, int64_t stride, int64_t n, float lr,
-                                            float b1, float b2, float eps, float wd, float t, float gm, void* sh = nullptr,
+                                            double b1d, double b2d, float eps, float wd, float t, float gm, void* sh = nullptr,
                                             int sh_dtype = SMOE_F16) {
-  const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
+  // every factor that holds 1 - beta comes from the double betas, rounded once (smoe_common.h)
+  const float b1 = (float)b1d, b2 = (float)b2d, one_minus_b1 = (float)(1.0 - b1d), one_minus_b2 = (float)(1.0 - b2d);
+  const bool low = one_minus_b1 < 0.5f;   // torch's lerp: from the end the weight is nearer to (beta1 = 0: exp_avg = g exactly)
+  float bc1, bc2_sqrt;
+  adam_bias(b1d, b2d, t, 1, bc1, bc2_sqrt);
   const float step_size = lr / bc1, decay = 1.0f - lr * wd;
   for (int64_t i = begin; i < end; i += stride) {
     if (i + 4 <= n) {
@@ -96,8 +106,8 @@ __device__ __forceinline__ void adamw_range(float* __restrict__ p, const GT* __r
       for (int q = 0; q < 4; ++q) {
         const float gq = gv[q] * gm;
         pv[q] *= decay;
-        mv[q] = mv[q] + (1.0f - b1) * (gq - mv[q]);          // exp_avg.lerp_(grad, 1 - beta1)
-        vv[q] = fmaf(vv[q], b2, (1.0f - b2) * gq * gq);      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+        mv[q] = adamw_lerp(mv[q], gq, one_minus_b1, b1, low);   // exp_avg.lerp_(grad, 1 - beta1)
+        vv[q] = fmaf(vv[q], b2, one_minus_b2 * gq * gq);        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
         const float denom = sqrtf(vv[q]) / bc2_sqrt + eps;
         pv[q] -= step_size * (mv[q] / denom);
       }
@@ -120,7 +130,7 @@ __device__ __forceinline__ void adamw_range(float* __restrict__ p, const GT* __r
         else if constexpr (std::is_same<GT, f16>::value) gq = (float)g[j];
         else gq = bf16_to_f32(g[j]);
         gq *= gm;
-        float pj = p[j] * decay, mj = m[j] + (1.0f - b1) * (gq - m[j]), vj = fmaf(v[j], b2, (1.0f - b2) * gq * gq);
+        float pj = p[j] * decay, mj = adamw_lerp(m[j], gq, one_minus_b1, b1, low), vj = fmaf(v[j], b2, one_minus_b2 * gq * gq);
         pj -= step_size * (mj / (sqrtf(vj) / bc2_sqrt + eps));
         p[j] = pj; m[j] = mj; v[j] = vj;
         if (sh) {
@@ -135,7 +145,7 @@ __device__ __forceinline__ void adamw_range(float* __restrict__ p, const GT* __r
 template <typename GT>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(float* __restrict__ p, const GT* __restrict__ g,
                                                             float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                            float b1, float b2, float eps, float wd,
+                                                            double b1, double b2, float eps, float wd,
                                                             const float* __restrict__ step, const float* __restrict__ grad_mult,
                                                             const float* __restrict__ found_inf) {
   if (found_inf && *found_inf != 0.f) return;   // GradScaler.step: a non-finite gradient skips the whole update
@@ -148,7 +158,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(float* __restrict__ 
 template <typename GT>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_multi_kernel(const int64_t* __restrict__ tab, const float* __restrict__ hyp,
                                                                   int n_t, const int32_t* __restrict__ blk, int64_t n_blocks,
-                                                                  float b1, float b2, float eps, const float* __restrict__ step,
+                                                                  double b1, double b2, float eps, const float* __restrict__ step,
                                                                   const float* __restrict__ grad_mult,
                                                                   const float* __restrict__ found_inf,
                                                                   const int64_t* __restrict__ shadow) {
@@ -253,8 +263,8 @@ extern "C" int smoe_grad_sumsq(const void* g, int g_dtype, int64_t n, const floa
   return 0;
 }
 
-extern "C" int smoe_adamw_step(float* p, const void* g, int g_dtype, float* m, float* v, int64_t n, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, const float* step, const float* grad_mult,
+extern "C" int smoe_adamw_step(float* p, const void* g, int g_dtype, float* m, float* v, int64_t n, float lr, double beta1,
+                               double beta2, float eps, float weight_decay, const float* step, const float* grad_mult,
                                const float* found_inf, void* stream) {
   SMOE_REQUIRE(n >= 0 && smoe_dtype_ok(g_dtype), "smoe_adamw_step: bad arguments");
   if (n == 0) return 0;
@@ -305,7 +315,7 @@ extern "C" int smoe_grad_sumsq_multi(const int64_t* tab, int n_tensors, const in
 }
 
 extern "C" int smoe_adamw_step_multi(const int64_t* tab, const float* hyp, int n_tensors, const int32_t* blk, int64_t n_blocks,
-                                     int g_dtype, float beta1, float beta2, float eps, const float* step, const float* grad_mult,
+                                     int g_dtype, double beta1, double beta2, float eps, const float* step, const float* grad_mult,
                                      const float* found_inf, const int64_t* shadow, void* stream) {
   SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31) && smoe_dtype_ok(g_dtype), "smoe_adamw_step_multi: bad arguments");
   if (n_blocks == 0) return 0;

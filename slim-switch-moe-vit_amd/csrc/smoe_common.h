@@ -193,3 +193,23 @@ inline bool smoe_ln_wave_layout(int d) {
   if (forced >= 0) return forced != 0;
   return d >= 768;
 }
+
+// ---- the scalar factors of the Adam-family steps (optim.hip, lamb.hip), from the betas as DOUBLES: taken in f32, 1 - 0.999^t is off by
+// 3e-5 at t = 1 and 1.0f - 0.999f by 1.3e-5 of itself (1e-4 for 0.9999) -- a common factor on every element of every update.
+// b^t for the whole number t the step counter holds
+__device__ __forceinline__ double pow_whole(double b, float t) {
+  unsigned n = t > 0.f ? (unsigned)t : 0u;
+  double r = 1.0;
+  while (n) {
+    if (n & 1u) r *= b;
+    b *= b;
+    n >>= 1;
+  }
+  return r;
+}
+
+// bc1 = 1 - beta1^t and sqrt(bc2) = sqrt(1 - beta2^t), each rounded once; both 1 without bias correction
+__device__ __forceinline__ void adam_bias(double b1, double b2, float t, int bias_correction, float& bc1, float& bc2_sqrt) {
+  bc1 = bias_correction ? (float)(1.0 - pow_whole(b1, t)) : 1.0f;
+  bc2_sqrt = bias_correction ? (float)sqrt(1.0 - pow_whole(b2, t)) : 1.0f;
+}

@@ -31,7 +31,7 @@ def test_bce_entry_points_are_declared_prototyped_and_exported_and_the_abi_is_29
         assert hasattr(lib, s), f"libslimmoe_hip.so does not export {s}"
         n_args = len([a for a in re.search(r"%s\s*\((.*?)\)" % s, text, re.S).group(1).split(",") if a.strip()])
         assert n_args == len(_lib.SIGNATURES[s][1]) == 9, s
-    assert _lib.ABI_VERSION == 29 and _lib.load().smoe_abi_version() == 29
+    assert _lib.ABI_VERSION == 30 and _lib.load().smoe_abi_version() == 30
 
 
 def test_bce_argument_checks_come_before_any_launch():

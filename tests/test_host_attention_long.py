@@ -27,7 +27,7 @@ def test_attention_entry_points_are_declared_exported_and_prototyped():
     for s in declared:
         assert hasattr(lib, s), f"libslimmoe_hip.so does not export {s}"
         assert s in _lib.SIGNATURES, f"_lib.SIGNATURES has no prototype for {s}"
-    assert _lib.ABI_VERSION == 29 and _lib.load().smoe_abi_version() == 29
+    assert _lib.ABI_VERSION == 30 and _lib.load().smoe_abi_version() == 30
     # the header no longer limits lse / the backward to N <= 256
     doc = text[text.index("int smoe_attention_fwd("):text.index("int smoe_attention_bwd(")]
     assert "N <= 256)" not in doc and "N <= 640" in doc

@@ -68,7 +68,7 @@ def test_three_entry_points_are_declared_exported_and_bound_under_abi_29():
         assert s in _lib.SIGNATURES and _lib.has_symbol(s), s
         decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % s, text).group(1)
         assert len(decl.split(",")) == len(_lib.SIGNATURES[s][1]), s
-    assert _lib.ABI_VERSION == 29 and _lib.load().smoe_abi_version() == 29
+    assert _lib.ABI_VERSION == 30 and _lib.load().smoe_abi_version() == 30
     assert "attention_skip.hip" in _lib._HASHED and _lib.source_build_id() == _lib.binary_build_id()
     for f in ("skip_plan", "attention_varlen", "skip_expand"):
         assert callable(getattr(ops, f))

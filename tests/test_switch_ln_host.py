@@ -43,7 +43,7 @@ def test_new_entry_points_are_declared_prototyped_and_exported_and_the_abi_stays
         n_args = len([a for a in re.search(r"%s\s*\((.*?)\)" % s, text, re.S).group(1).split(",") if a.strip()])
         assert n_args == len(_lib.SIGNATURES[s][1]), s
     assert "models/layers.py:31-157" in open(HEADER).read()
-    assert _lib.ABI_VERSION == 29 and _lib.load().smoe_abi_version() == 29
+    assert _lib.ABI_VERSION == 30 and _lib.load().smoe_abi_version() == 30
     assert _lib.binary_build_id() == _lib.source_build_id()
 
 
