@@ -819,6 +819,30 @@ int smoe_switch_ln_bwd(const float* x, const void* dy, int dy_dtype, const float
                        int64_t T, int d, int K, float* dx, float* dweights, float* dbiases, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---- counter-based dropout (main.py --drop: pos_drop, proj_drop, the experts' Dropout behind GELU) --------------------------------
+ * The mask is a pure function of (key, first_block, element index): nothing is stored for the backward, which calls smoe_dropout on
+ * the gradient with the forward's key (dx = dropout_same_key(dy)), and the host can reproduce every mask bit (tests/_dropout_cases.py).
+ * THE RULE: Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85.  key: DEVICE int64 [2] =
+ * (k, c), read from memory as uint64 by every launch (never by value: a replayed graph sees the key its replay drew).  Elements are
+ * numbered row-major over the logical [rows, cols] tensor; element e lies in block b = first_block + e / 8 (first_block: 0, or the
+ * number of 8-element blocks in front of this piece of a larger tensor).  Block b: Philox key (lo32 k, hi32 k), counter (lo32 b, hi32
+ * b, lo32 c, hi32 c) -> r0..r3; element 8 b + 2 j + h (j 0..3, h 0..1) draws u = (r_j >> 16 h) & 0xffff and is KEPT iff u < thr16.
+ * thr16 = round((1 - p) * 65536) in [0, 65536]; scale = (float)(65536.0 / thr16) formed in double on the host (0 for thr16 == 0): the
+ * inverse of the keep probability really applied.  f32 arithmetic, one rounding per operation: t = f32(x) * scale; with row_scale
+ * (f32 [rows]) t = t * row_scale[row]; a dropped element is SELECTED to +0.0 (a dropped NaN / inf gives 0, a kept one propagates);
+ * smoe_dropout_add then forms residual + t; one round-to-nearest-even into the output dtype.  The mask does not depend on the grid,
+ * the dtypes, or on which of the two entry points runs.
+ * smoe_dropout     : y [rows, cols] (dtype_out) from x (dtype_in), any pairing of f32 / f16 / bf16; y may be x when the dtypes are equal.
+ * smoe_dropout_add : out f32 = residual f32 + t(h); h f32 / f16 / bf16; out may be residual (never h).
+ * cols % 8 == 0, cols > 0; rows >= 0 (0 returns at once); rows * cols * 4 must fit in int64; x, y, h, residual, out 16-byte aligned, key
+ * 8-byte aligned.  Null pointers, sizes, thr16 > 65536, dtype codes and alignment are refused with a message before any launch.  One
+ * launch of 256-thread workgroups (at most 4096, a grid stride behind that), 8 elements per lane and trip; no LDS, no atomics, no
+ * allocation, no host read: both can be captured.                                                                                 */
+int smoe_dropout(const void* x, void* y, const float* row_scale, const int64_t* key, uint64_t first_block, int64_t rows, int64_t cols,
+                 uint32_t thr16, float scale, int dtype_in, int dtype_out, void* stream);
+int smoe_dropout_add(const void* h, const float* residual, const float* row_scale, float* out, const int64_t* key,
+                     uint64_t first_block, int64_t rows, int64_t cols, uint32_t thr16, float scale, int dtype_h, void* stream);
+
 /* ---- small helpers ------------------------------------------------------------------------------------
  * elementwise cast between dtypes (weight shadow copies; not on the per-step path)                  */
 int smoe_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);

@@ -176,6 +176,10 @@ SIGNATURES = {
     "smoe_switch_ln_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "smoe_switch_ln_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_int64, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "smoe_dropout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_int64, c_int64, ctypes.c_uint32,
+                             ctypes.c_float, c_int, c_int, c_void_p]),
+    "smoe_dropout_add": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_int64, c_int64, ctypes.c_uint32,
+                                 ctypes.c_float, c_int, c_void_p]),
 }
 
 # entry points that only an optional build holds (`make FFN=-DSMOE_FFN_FUSED`): bound when present, never required
@@ -185,7 +189,7 @@ _lib = None
 
 # what csrc/Makefile hashes into smoe_build_id(): the same names, sorted as strings, relative to csrc/
 _HASHED = ["api.hip", "router.hip", "router16.hip", "gate.hip", "soft_gate.hip", "dispatch.hip", "gemm.hip", "backward.hip", "attention.hip",
-           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "lamb.hip", "gshard.hip", "noisy_gate.hip", "attention_skip.hip", "switch_ln.hip", "smoe_common.h", "attention_tile.h", "wave_row4.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
+           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "lamb.hip", "gshard.hip", "noisy_gate.hip", "attention_skip.hip", "switch_ln.hip", "dropout.hip", "smoe_common.h", "attention_tile.h", "wave_row4.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
            "../../include/slimmoe.h", "Makefile"]
 
 

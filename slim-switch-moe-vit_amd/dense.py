@@ -14,6 +14,10 @@ attention, forward and backward.  Here:
                   dW = dY^T X by smoe_grouped_wgrad_rows with one group, db = smoe_group_colsum
     AttentionFn   forward = smoe_attention_fwd on the fused [B, N, 3, H, 64] qkv layout;
                   backward = smoe_attention_bwd (scores recomputed per (image, head); dqkv in the same fused layout)
+    DropoutFn     forward = smoe_dropout (counter-based mask of a 16-byte device key; optionally in place, optionally a per-row factor);
+                  backward = the same call on the gradient with the saved key -- no mask is stored
+    DropoutAddFn  forward = smoe_dropout_add (f32 residual + per-row factor x dropout(h) in one pass: the attention half's tail with
+                  projection dropout); backward: d residual = dout, dh = smoe_dropout(dout) with the saved key
 
 Shapes the kernels do not cover are reported by ``supported_*`` so that the caller keeps torch's path for them (loudly:
 vit.SlimMoEFallbackWarning)."""
@@ -194,6 +198,51 @@ def linear_supported(x16: torch.Tensor, weight: torch.Tensor) -> bool:
     N = weight.shape[0]
     return (x16.is_cuda and x16.dtype == torch.float16 and x16.is_contiguous() and M > 0 and K % 64 == 0 and N >= 1
             and weight.dim() >= 2 and weight.numel() == N * K)
+
+
+class DropoutFn(torch.autograd.Function):
+    """``dropout(x, p)`` on the counter-based kernel (ops.dropout: the mask is a function of the 16-byte key and the element index).
+    Nothing of x's size is saved: the backward regenerates the mask, ``dx = dropout_same_key(dy)``.  ``key`` (int64 [2], device): drawn
+    from torch's generator when None; ``row_scale`` (f32 [rows], no gradient) multiplies row r; ``inplace`` overwrites x."""
+
+    @staticmethod
+    def forward(ctx, x, p, key=None, row_scale=None, inplace=False, out_dtype=None):
+        if key is None:
+            key = ops.dropout_key(x.device)
+        ctx.p, ctx.in_dtype, ctx.has_scale = p, x.dtype, row_scale is not None
+        ctx.save_for_backward(key, row_scale if row_scale is not None else torch.empty(0, device=x.device))
+        if inplace:
+            ctx.mark_dirty(x)
+            return ops.dropout(x, key, p, row_scale=row_scale, out=x)
+        return ops.dropout(x, key, p, out_dtype=out_dtype, row_scale=row_scale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        key, row_scale = ctx.saved_tensors
+        dx = ops.dropout(dy.contiguous(), key, ctx.p, out_dtype=ctx.in_dtype, row_scale=row_scale if ctx.has_scale else None)
+        return dx, None, None, None, None, None
+
+
+class DropoutAddFn(torch.autograd.Function):
+    """``residual + row_scale[r] * dropout(h, p)`` in f32, one pass (ops.dropout_add): the attention half's tail
+    ``x + drop_path(proj_drop(proj(o)))`` (models/vision_transformer.py:279, 320).  Saves the key and ``row_scale`` only; the
+    residual's gradient is the output's, h's is the same dropout of it."""
+
+    @staticmethod
+    def forward(ctx, h, residual, p, key=None, row_scale=None):
+        if key is None:
+            key = ops.dropout_key(h.device)
+        ctx.p, ctx.h_dtype, ctx.has_scale = p, h.dtype, row_scale is not None
+        ctx.save_for_backward(key, row_scale if row_scale is not None else torch.empty(0, device=h.device))
+        return ops.dropout_add(h, residual, key, p, row_scale=row_scale)
+
+    @staticmethod
+    def backward(ctx, dout):
+        key, row_scale = ctx.saved_tensors
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh = ops.dropout(dout.contiguous(), key, ctx.p, out_dtype=ctx.h_dtype, row_scale=row_scale if ctx.has_scale else None)
+        return dh, (dout if ctx.needs_input_grad[1] else None), None, None, None
 
 
 class AttentionFn(torch.autograd.Function):

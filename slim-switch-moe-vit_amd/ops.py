@@ -7,6 +7,7 @@ Shapes / dtypes / contiguity are validated here, before the C call (SURVEY.md 8b
 from __future__ import annotations
 
 import ctypes
+import functools
 from typing import Optional
 
 import torch
@@ -1115,6 +1116,83 @@ def cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     rc = lib.smoe_cast(_ptr(src), dtype_code(src.dtype), _ptr(dst), dtype_code(dtype), src.numel(), _stream(src))
     _lib.check(rc, "smoe_cast")
     return dst
+
+
+# ------------------------------------------------------------------------------------------ counter-based dropout
+@functools.lru_cache(maxsize=64)
+def dropout_params(p: float):
+    """``(thr16, scale)`` of a drop probability: an element is kept iff its 16-bit draw is below ``thr16 = round((1 - p) * 65536)``
+    (ties to even: p = 1 - 2^-17 keeps nothing) and kept values are multiplied by ``scale = f32(65536 / thr16)`` -- the inverse of
+    the keep probability really applied, so the expectation is unbiased; 0 when nothing is kept."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    thr16 = min(65536, max(0, int(round((1.0 - p) * 65536.0))))
+    scale = 65536.0 / thr16 if thr16 else 0.0
+    return thr16, torch.tensor(scale, dtype=torch.float64).float().item()   # rounded once to f32, as the C call will pass it
+
+
+def dropout_key(device) -> torch.Tensor:
+    """A fresh mask key: int64 [2] = (k, c) on ``device``, ONE draw from torch's generator (``torch.manual_seed`` reproduces a run; a
+    captured draw advances on every replay, as the captured ``randn`` / ``bernoulli_`` draws do).  The kernels read it from memory."""
+    return torch.randint(-(1 << 63), (1 << 63) - 1, (2,), dtype=torch.int64, device=device)
+
+
+def _drop_args(x: torch.Tensor, key: torch.Tensor, row_scale, name: str):
+    _chk(x, name)
+    _chk(key, "key", torch.int64, align=8)
+    if key.numel() != 2:
+        raise ValueError(f"dropout key: int64 [2], got {tuple(key.shape)}")
+    if x.dim() < 1 or x.shape[-1] % 8 or x.shape[-1] == 0:
+        raise ValueError(f"{name}: the last dimension must be a positive multiple of 8, got {tuple(x.shape)}")
+    cols = x.shape[-1]
+    rows = x.numel() // cols
+    if row_scale is not None:
+        _chk(row_scale, "row_scale", torch.float32, align=4)
+        if row_scale.numel() != rows:
+            raise ValueError(f"row_scale: {rows} rows expected, got {tuple(row_scale.shape)}")
+    return rows, cols
+
+
+def dropout(x: torch.Tensor, key: torch.Tensor, p: float, out_dtype: Optional[torch.dtype] = None, row_scale=None,
+            out: Optional[torch.Tensor] = None, first_block: int = 0) -> torch.Tensor:
+    """``select(kept, x * scale [* row_scale[row]], +0)`` in ``out_dtype`` (default: x's) with the mask of ``key`` (include/slimmoe.h:
+    the rule).  Rows are the leading dimensions, the last dimension (a multiple of 8) the columns.  ``out=x`` runs in place.  The
+    backward of a dropout IS this call on the gradient with the same key.  ``first_block``: the number of 8-element blocks in front
+    of ``x`` when it is a row piece of a larger tensor."""
+    rows, cols = _drop_args(x, key, row_scale, "x")
+    thr16, scale = dropout_params(p)
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
+    else:
+        _chk(out, "out", out_dtype)
+        if out.shape != x.shape:
+            raise ValueError(f"out: shape {tuple(x.shape)} expected, got {tuple(out.shape)}")
+    rc = _lib.load().smoe_dropout(_ptr(x), _ptr(out), _ptr(row_scale), _ptr(key), int(first_block) & 0xFFFFFFFFFFFFFFFF, rows, cols,
+                                  thr16, scale, dtype_code(x.dtype), dtype_code(out.dtype), _stream(x))
+    _lib.check(rc, "smoe_dropout")
+    return out
+
+
+def dropout_add(h: torch.Tensor, residual: torch.Tensor, key: torch.Tensor, p: float, row_scale=None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``residual + select(kept, h * scale [* row_scale[row]], +0)``, f32: the attention half's tail ``x + drop_path(proj_drop(h))`` in
+    one pass.  ``out=residual`` runs in place."""
+    rows, cols = _drop_args(h, key, row_scale, "h")
+    _chk(residual, "residual", torch.float32)
+    if residual.shape != h.shape:
+        raise ValueError(f"residual: shape {tuple(h.shape)} expected, got {tuple(residual.shape)}")
+    thr16, scale = dropout_params(p)
+    if out is None:
+        out = torch.empty_like(residual)
+    else:
+        _chk(out, "out", torch.float32)
+        if out.shape != h.shape:
+            raise ValueError(f"out: shape {tuple(h.shape)} expected, got {tuple(out.shape)}")
+    rc = _lib.load().smoe_dropout_add(_ptr(h), _ptr(residual), _ptr(row_scale), _ptr(out), _ptr(key), 0, rows, cols, thr16, scale,
+                                      dtype_code(h.dtype), _stream(h))
+    _lib.check(rc, "smoe_dropout_add")
+    return out
 
 
 def transpose_cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
