@@ -189,7 +189,7 @@ _lib = None
 
 # what csrc/Makefile hashes into smoe_build_id(): the same names, sorted as strings, relative to csrc/
 _HASHED = ["api.hip", "router.hip", "router16.hip", "gate.hip", "soft_gate.hip", "dispatch.hip", "gemm.hip", "backward.hip", "attention.hip",
-           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "lamb.hip", "gshard.hip", "noisy_gate.hip", "attention_skip.hip", "switch_ln.hip", "dropout.hip", "smoe_common.h", "attention_tile.h", "wave_row4.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
+           "optim.hip", "comm.hip", "dense_bwd.hip", "attention_bwd.hip", "embed.hip", "loss.hip", "lamb.hip", "gshard.hip", "noisy_gate.hip", "attention_skip.hip", "switch_ln.hip", "dropout.hip", "smoe_common.h", "attention_tile.h", "wave_row4.h", "optim_table.h", "router16_kernel.h", "router_mt_kernel.h", "router_launch.h", "gemm_persistent.h",
            "../../include/slimmoe.h", "Makefile"]
 
 

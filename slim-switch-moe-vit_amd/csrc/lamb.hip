@@ -13,13 +13,9 @@
 // as stage 2 re-reading exp_avg and exp_avg_sq, and would add a third to the optimizer's memory.  Every sum has a fixed order (f32
 // inside a block: thread, wave, workgroup; double across blocks), so a step is reproducible bit for bit and a tensor's update does
 // not depend on what else is in the launch.  Every kernel returns at once when *found_inf != 0 (GradScaler.step).
-#include "smoe_common.h"
-#include <type_traits>
+#include "optim_table.h"
 
 namespace {
-
-constexpr int LAMB_THREADS = 256;
-constexpr int LAMB_BLOCK = 16384;   // elements per workgroup: optim.hip's SUMSQ_BLOCK (optim._block_table builds blk for both)
 
 // THE update of one element before the trust ratio: stage 1 sums its square, stage 2 applies it -- one function, so the same bits
 __device__ __forceinline__ float lamb_update(float p, float m, float v, float bc1, float bc2_sqrt, float eps, float wd) {
@@ -27,25 +23,18 @@ __device__ __forceinline__ float lamb_update(float p, float m, float v, float bc
   return wd != 0.f ? fmaf(wd, p, u) : u;
 }
 
-template <typename GT>
-__device__ __forceinline__ float grad_at(const GT* __restrict__ g, int64_t j) {
-  if constexpr (std::is_same<GT, float>::value) return g[j];
-  else if constexpr (std::is_same<GT, f16>::value) return (float)g[j];
-  else return bf16_to_f32(g[j]);
-}
-
 // out[0] = clip, out[1] = G = sqrt(sum of the partials) * *num / *den (NULL = 1); max_grad_norm <= 0: no clipping
-__global__ __launch_bounds__(LAMB_THREADS) void lamb_clip_kernel(const float* __restrict__ partial, int64_t n,
+__global__ __launch_bounds__(OPT_THREADS) void lamb_clip_kernel(const float* __restrict__ partial, int64_t n,
                                                                  const float* __restrict__ num, const float* __restrict__ den,
                                                                  float max_grad_norm, const float* __restrict__ found_inf,
                                                                  float* __restrict__ out) {
   if (found_inf && *found_inf != 0.f) return;
-  __shared__ double red[LAMB_THREADS];
+  __shared__ double red[OPT_THREADS];
   double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += LAMB_THREADS) acc += (double)partial[i];
+  for (int64_t i = threadIdx.x; i < n; i += OPT_THREADS) acc += (double)partial[i];
   red[threadIdx.x] = acc;
   __syncthreads();
-  for (int s = LAMB_THREADS / 2; s > 0; s >>= 1) {
+  for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
@@ -57,7 +46,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_clip_kernel(const float* __
 }
 
 template <typename GT>
-__global__ __launch_bounds__(LAMB_THREADS) void lamb_stage1_multi_kernel(const int64_t* __restrict__ tab, const float* __restrict__ hyp,
+__global__ __launch_bounds__(OPT_THREADS) void lamb_stage1_multi_kernel(const int64_t* __restrict__ tab, const float* __restrict__ hyp,
                                                                          int n_t, const int32_t* __restrict__ blk, int64_t n_blocks,
                                                                          double b1d, double b2d, float beta3, float eps,
                                                                          int bias_correction, const float* __restrict__ step,
@@ -66,16 +55,14 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage1_multi_kernel(const i
                                                                          const float* __restrict__ found_inf,
                                                                          float* __restrict__ norms) {
   if (found_inf && *found_inf != 0.f) return;
-  const int t = blk[blockIdx.x];
-  if (t < 0 || t >= n_t) return;   // the table is caller data
-  __shared__ float red[2][LAMB_THREADS / 64];
-  float* __restrict__ p = reinterpret_cast<float*>(tab[t]);
-  const GT* __restrict__ g = reinterpret_cast<const GT*>(tab[(int64_t)n_t + t]);
-  float* __restrict__ m = reinterpret_cast<float*>(tab[2ll * n_t + t]);
-  float* __restrict__ v = reinterpret_cast<float*>(tab[3ll * n_t + t]);
-  const int64_t n = tab[4ll * n_t + t];
-  const int64_t base = (int64_t)blk[n_blocks + blockIdx.x] * LAMB_BLOCK;
-  const int64_t end = base + LAMB_BLOCK < n ? base + LAMB_BLOCK : n;
+  int t;
+  if (!opt_tensor(blk, n_t, t)) return;
+  __shared__ float red[2][OPT_THREADS / 64];
+  float* __restrict__ p = opt_row<float, 0>(tab, n_t, t);
+  const GT* __restrict__ g = opt_row<const GT, 1>(tab, n_t, t);
+  float* __restrict__ m = opt_row<float, 2>(tab, n_t, t);
+  float* __restrict__ v = opt_row<float, 3>(tab, n_t, t);
+  const int64_t n = opt_entry<4>(tab, n_t, t), base = opt_base(blk, n_blocks), end = opt_end(base, n);
   const float wd = hyp[(int64_t)n_t + t];
   const bool adapt = hyp[2ll * n_t + t] != 0.f;
   const float b1 = (float)b1d, b2 = (float)b2d, one_minus_b2 = (float)(1.0 - b2d);   // (1.0f - 0.999f is off by 1.3e-5 of itself)
@@ -83,7 +70,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage1_multi_kernel(const i
   float bc1, bc2_sqrt;
   adam_bias(b1d, b2d, *step, bias_correction, bc1, bc2_sqrt);   // *step: already advanced for this update
   float pp = 0.f, uu = 0.f;
-  for (int64_t i = base + threadIdx.x * 4; i < end; i += LAMB_THREADS * 4) {
+  for (int64_t i = base + threadIdx.x * 4; i < end; i += OPT_THREADS * 4) {
     if (i + 4 <= n) {
       float gv[4];
       load4(g + i, gv);
@@ -118,20 +105,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage1_multi_kernel(const i
     }
   }
   if (!adapt) return;   // (uniform over the workgroup: its trust ratio is 1 and nobody reads its partials)
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    pp += __shfl_xor(pp, s, 64);
-    uu += __shfl_xor(uu, s, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = pp;
-    red[1][threadIdx.x >> 6] = uu;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    norms[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    norms[n_blocks + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
+  wg_sum2_to(pp, uu, red, norms + blockIdx.x, norms + n_blocks + blockIdx.x);
 }
 
 // one wave per tensor: its block partials in block order (lane l takes blocks l, l + 64, ...; then the xor tree), in double
@@ -166,7 +140,7 @@ __global__ __launch_bounds__(64) void lamb_trust_multi_kernel(const float* __res
   }
 }
 
-__global__ __launch_bounds__(LAMB_THREADS) void lamb_stage2_multi_kernel(const int64_t* __restrict__ tab, const float* __restrict__ hyp,
+__global__ __launch_bounds__(OPT_THREADS) void lamb_stage2_multi_kernel(const int64_t* __restrict__ tab, const float* __restrict__ hyp,
                                                                          int n_t, const int32_t* __restrict__ blk, int64_t n_blocks,
                                                                          double b1d, double b2d, float eps, int bias_correction,
                                                                          const float* __restrict__ step,
@@ -174,46 +148,37 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage2_multi_kernel(const i
                                                                          const float* __restrict__ found_inf,
                                                                          const int64_t* __restrict__ shadow) {
   if (found_inf && *found_inf != 0.f) return;
-  const int t = blk[blockIdx.x];
-  if (t < 0 || t >= n_t) return;   // the table is caller data
-  float* __restrict__ p = reinterpret_cast<float*>(tab[t]);
-  const float* __restrict__ m = reinterpret_cast<const float*>(tab[2ll * n_t + t]);
-  const float* __restrict__ v = reinterpret_cast<const float*>(tab[3ll * n_t + t]);
-  const int64_t n = tab[4ll * n_t + t];
-  const int64_t base = (int64_t)blk[n_blocks + blockIdx.x] * LAMB_BLOCK;
-  const int64_t end = base + LAMB_BLOCK < n ? base + LAMB_BLOCK : n;
+  int t;
+  if (!opt_tensor(blk, n_t, t)) return;
+  float* __restrict__ p = opt_row<float, 0>(tab, n_t, t);
+  const float* __restrict__ m = opt_row<const float, 2>(tab, n_t, t);
+  const float* __restrict__ v = opt_row<const float, 3>(tab, n_t, t);
+  const int64_t n = opt_entry<4>(tab, n_t, t), base = opt_base(blk, n_blocks), end = opt_end(base, n);
   const float lr = hyp[t], wd = hyp[(int64_t)n_t + t], r = trust[t];
-  void* sh = shadow ? reinterpret_cast<void*>(shadow[t]) : nullptr;
-  const int sh_dtype = shadow ? (int)shadow[(int64_t)n_t + t] : SMOE_F16;
+  void* sh = opt_image(shadow, t);
+  const int sh_dtype = opt_image_dtype(shadow, n_t, t);
   float bc1, bc2_sqrt;
   adam_bias(b1d, b2d, *step, bias_correction, bc1, bc2_sqrt);
-  for (int64_t i = base + threadIdx.x * 4; i < end; i += LAMB_THREADS * 4) {
+  for (int64_t i = base + threadIdx.x * 4; i < end; i += OPT_THREADS * 4) {
     if (i + 4 <= n) {
       f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
       const f32x4 mv = *reinterpret_cast<const f32x4*>(m + i), vv = *reinterpret_cast<const f32x4*>(v + i);
 #pragma unroll
       for (int q = 0; q < 4; ++q) pv[q] -= lr * (r * lamb_update(pv[q], mv[q], vv[q], bc1, bc2_sqrt, eps, wd));
       *reinterpret_cast<f32x4*>(p + i) = pv;
-      if (sh) {
-        if (sh_dtype == SMOE_F16) {
-          f16x4 h; h[0] = (f16)pv[0]; h[1] = (f16)pv[1]; h[2] = (f16)pv[2]; h[3] = (f16)pv[3];
-          *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(sh) + i) = h;
-        } else {
-          s16x4 h; h[0] = (short)f32_to_bf16(pv[0]); h[1] = (short)f32_to_bf16(pv[1]); h[2] = (short)f32_to_bf16(pv[2]); h[3] = (short)f32_to_bf16(pv[3]);
-          *reinterpret_cast<s16x4*>(reinterpret_cast<bf16_bits*>(sh) + i) = h;
-        }
-      }
+      image_store4(sh, sh_dtype, i, pv);
     } else {
       for (int64_t j = i; j < n; ++j) {
         const float pj = p[j] - lr * (r * lamb_update(p[j], m[j], v[j], bc1, bc2_sqrt, eps, wd));
         p[j] = pj;
-        if (sh) {
-          if (sh_dtype == SMOE_F16) reinterpret_cast<f16*>(sh)[j] = (f16)pj;
-          else reinterpret_cast<bf16_bits*>(sh)[j] = f32_to_bf16(pj);
-        }
+        image_store1(sh, sh_dtype, j, pj);
       }
     }
   }
+}
+
+static inline bool lamb_hyper_ok(double beta1, double beta2, float eps) {
+  return beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f;
 }
 
 }  // namespace
@@ -222,7 +187,7 @@ extern "C" int smoe_lamb_clip(const float* partial, int64_t n_partials, const fl
                               float max_grad_norm, const float* found_inf, float* out, void* stream) {
   SMOE_REQUIRE(n_partials >= 0 && n_partials < (1ll << 31), "smoe_lamb_clip: bad arguments");
   SMOE_REQUIRE(out && (partial || n_partials == 0), "smoe_lamb_clip: null pointer");
-  hipLaunchKernelGGL(lamb_clip_kernel, dim3(1), dim3(LAMB_THREADS), 0, (hipStream_t)stream, partial, n_partials, mult_num, mult_den,
+  hipLaunchKernelGGL(lamb_clip_kernel, dim3(1), dim3(OPT_THREADS), 0, (hipStream_t)stream, partial, n_partials, mult_num, mult_den,
                      max_grad_norm, found_inf, out);
   SMOE_CHECK_LAUNCH("smoe_lamb_clip");
   return 0;
@@ -232,24 +197,21 @@ extern "C" int smoe_lamb_stage1_multi(const int64_t* tab, const float* hyp, int 
                                       int g_dtype, double beta1, double beta2, float beta3, float eps, int bias_correction,
                                       const float* step, const float* grad_mult, const float* clip, const float* found_inf,
                                       float* norms, void* stream) {
-  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31) && smoe_dtype_ok(g_dtype) && beta1 >= 0.0 && beta1 < 1.0 &&
-               beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f, "smoe_lamb_stage1_multi: bad arguments");
+  SMOE_REQUIRE(opt_multi_ok(n_tensors, n_blocks, g_dtype) && lamb_hyper_ok(beta1, beta2, eps), "smoe_lamb_stage1_multi: bad arguments");
   if (n_blocks == 0) return 0;
   SMOE_REQUIRE(tab && hyp && blk && step && norms, "smoe_lamb_stage1_multi: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)n_blocks), block(LAMB_THREADS);
-  switch (g_dtype) {
-    case SMOE_F32: hipLaunchKernelGGL(lamb_stage1_multi_kernel<float>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, beta3, eps, bias_correction, step, grad_mult, clip, found_inf, norms); break;
-    case SMOE_F16: hipLaunchKernelGGL(lamb_stage1_multi_kernel<f16>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, beta3, eps, bias_correction, step, grad_mult, clip, found_inf, norms); break;
-    default: hipLaunchKernelGGL(lamb_stage1_multi_kernel<bf16_bits>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, beta3, eps, bias_correction, step, grad_mult, clip, found_inf, norms); break;
-  }
+  opt_dispatch_grad(g_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(lamb_stage1_multi_kernel<typename decltype(tag)::T>, dim3((unsigned)n_blocks), dim3(OPT_THREADS), 0,
+                       (hipStream_t)stream, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, beta3, eps, bias_correction, step, grad_mult,
+                       clip, found_inf, norms);
+  });
   SMOE_CHECK_LAUNCH("smoe_lamb_stage1_multi");
   return 0;
 }
 
 extern "C" int smoe_lamb_trust_multi(const float* norms, int64_t n_blocks, const int32_t* first, const float* hyp, int n_tensors,
                                      int trust_clip, const float* found_inf, float* trust, void* stream) {
-  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31), "smoe_lamb_trust_multi: bad arguments");
+  SMOE_REQUIRE(opt_multi_ok(n_tensors, n_blocks), "smoe_lamb_trust_multi: bad arguments");
   if (n_tensors == 0) return 0;
   SMOE_REQUIRE(norms && first && hyp && trust, "smoe_lamb_trust_multi: null pointer");
   hipLaunchKernelGGL(lamb_trust_multi_kernel, dim3((unsigned)n_tensors), dim3(64), 0, (hipStream_t)stream, norms, n_blocks, first, hyp,
@@ -261,11 +223,10 @@ extern "C" int smoe_lamb_trust_multi(const float* norms, int64_t n_blocks, const
 extern "C" int smoe_lamb_stage2_multi(const int64_t* tab, const float* hyp, int n_tensors, const int32_t* blk, int64_t n_blocks,
                                       double beta1, double beta2, float eps, int bias_correction, const float* step,
                                       const float* trust, const float* found_inf, const int64_t* shadow, void* stream) {
-  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31) && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 &&
-               beta2 < 1.0 && eps >= 0.f, "smoe_lamb_stage2_multi: bad arguments");
+  SMOE_REQUIRE(opt_multi_ok(n_tensors, n_blocks) && lamb_hyper_ok(beta1, beta2, eps), "smoe_lamb_stage2_multi: bad arguments");
   if (n_blocks == 0) return 0;
   SMOE_REQUIRE(tab && hyp && blk && step && trust, "smoe_lamb_stage2_multi: null pointer");
-  hipLaunchKernelGGL(lamb_stage2_multi_kernel, dim3((unsigned)n_blocks), dim3(LAMB_THREADS), 0, (hipStream_t)stream, tab, hyp,
+  hipLaunchKernelGGL(lamb_stage2_multi_kernel, dim3((unsigned)n_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, tab, hyp,
                      n_tensors, blk, n_blocks, beta1, beta2, eps, bias_correction, step, trust, found_inf, shadow);
   SMOE_CHECK_LAUNCH("smoe_lamb_stage2_multi");
   return 0;

@@ -10,23 +10,19 @@
 //   smoe_amp_update   : GradScaler.update() (growth / backoff of the loss scale) + the optimizer's step counter
 //   smoe_ema_update_multi : the weight EMA after the step (timm ModelEma.update), every tensor in one launch, skippable from the device
 // LAMB (timm.optim.Lamb: --opt lamb) reads the same tables -- and the block partials of smoe_grad_sumsq_multi -- from lamb.hip.
-#include "smoe_common.h"
-#include <type_traits>
+#include "optim_table.h"
 
 namespace {
-
-constexpr int OPT_THREADS = 256;
-constexpr int SUMSQ_BLOCK = 16384;  // elements per workgroup of the norm pass
 
 // one 16K-element block of one gradient: sum of squares of (g * mul) -> partial[slot]; non-finite -> *found_inf = 1
 template <typename GT>
 __device__ __forceinline__ void sumsq_block(const GT* __restrict__ g, int64_t n, int64_t block, float mul, float* __restrict__ partial_slot,
                                             float* __restrict__ found_inf) {
   __shared__ float red[OPT_THREADS / 64];
-  const int64_t base = block * SUMSQ_BLOCK;
+  const int64_t base = block * OPT_BLOCK;
   float acc = 0.f;
   bool bad = false;
-  for (int i = threadIdx.x * 8; i < SUMSQ_BLOCK; i += OPT_THREADS * 8) {
+  for (int i = threadIdx.x * 8; i < OPT_BLOCK; i += OPT_THREADS * 8) {
     const int64_t at = base + i;
     if (at + 8 <= n) {
       float v[8];
@@ -39,20 +35,14 @@ __device__ __forceinline__ void sumsq_block(const GT* __restrict__ g, int64_t n,
       }
     } else {
       for (int64_t j = at; j < n && j < at + 8; ++j) {
-        float u;
-        if constexpr (std::is_same<GT, float>::value) u = g[j] * mul;
-        else if constexpr (std::is_same<GT, f16>::value) u = (float)g[j] * mul;
-        else u = bf16_to_f32(g[j]) * mul;
+        const float u = grad_at<GT>(g, j) * mul;
         bad |= !(fabsf(u) <= 3.4028234664e38f);
         acc = fmaf(u, u, acc);
       }
     }
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   if (__ballot(bad) && (threadIdx.x & 63) == 0 && found_inf) *found_inf = 1.0f;
-  __syncthreads();
-  if (threadIdx.x == 0) *partial_slot = (red[0] + red[1]) + (red[2] + red[3]);
+  wg_sum_to(acc, red, partial_slot);
 }
 
 template <typename GT>
@@ -64,16 +54,16 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_sumsq_kernel(const GT* __res
 
 // MULTI-TENSOR forms: one launch for every gradient / parameter of the step (a ViT-B/16 MoE has ~180 parameter tensors; one
 // launch each left the optimizer step bound by launch overhead).  tab = int64 [5][n_t]: rows p, g, m, v (addresses) and n;
-// blk = int32 [2][n_blocks]: tensor of workgroup b, 16K-element block inside it.  Same blocks, same arithmetic, same order of
-// the partial sums as the single-tensor forms.
+// blk = int32 [2][n_blocks]: tensor of workgroup b, 16K-element block inside it (optim_table.h).  Same blocks, same arithmetic,
+// same order of the partial sums as the single-tensor forms.
 template <typename GT>
 __global__ __launch_bounds__(OPT_THREADS) void grad_sumsq_multi_kernel(const int64_t* __restrict__ tab, int n_t,
                                                                        const int32_t* __restrict__ blk, int64_t n_blocks,
                                                                        const float* __restrict__ inv_scale,
                                                                        float* __restrict__ partial, float* __restrict__ found_inf) {
-  const int t = blk[blockIdx.x];
-  if (t < 0 || t >= n_t) return;   // the table is caller data
-  sumsq_block<GT>(reinterpret_cast<const GT*>(tab[(int64_t)n_t + t]), tab[4ll * n_t + t], blk[n_blocks + blockIdx.x],
+  int t;
+  if (!opt_tensor(blk, n_t, t)) return;
+  sumsq_block<GT>(opt_row<const GT, 1>(tab, n_t, t), opt_entry<4>(tab, n_t, t), blk[n_blocks + blockIdx.x],
                   inv_scale ? *inv_scale : 1.0f, partial + blockIdx.x, found_inf);
 }
 
@@ -114,29 +104,14 @@ __device__ __forceinline__ void adamw_range(float* __restrict__ p, const GT* __r
       *reinterpret_cast<f32x4*>(p + i) = pv;
       *reinterpret_cast<f32x4*>(m + i) = mv;
       *reinterpret_cast<f32x4*>(v + i) = vv;
-      if (sh) {
-        if (sh_dtype == SMOE_F16) {
-          f16x4 h; h[0] = (f16)pv[0]; h[1] = (f16)pv[1]; h[2] = (f16)pv[2]; h[3] = (f16)pv[3];
-          *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(sh) + i) = h;
-        } else {
-          s16x4 h; h[0] = (short)f32_to_bf16(pv[0]); h[1] = (short)f32_to_bf16(pv[1]); h[2] = (short)f32_to_bf16(pv[2]); h[3] = (short)f32_to_bf16(pv[3]);
-          *reinterpret_cast<s16x4*>(reinterpret_cast<bf16_bits*>(sh) + i) = h;
-        }
-      }
+      image_store4(sh, sh_dtype, i, pv);
     } else {
       for (int64_t j = i; j < n; ++j) {
-        float gq;
-        if constexpr (std::is_same<GT, float>::value) gq = g[j];
-        else if constexpr (std::is_same<GT, f16>::value) gq = (float)g[j];
-        else gq = bf16_to_f32(g[j]);
-        gq *= gm;
+        const float gq = grad_at<GT>(g, j) * gm;
         float pj = p[j] * decay, mj = adamw_lerp(m[j], gq, one_minus_b1, b1, low), vj = fmaf(v[j], b2, one_minus_b2 * gq * gq);
         pj -= step_size * (mj / (sqrtf(vj) / bc2_sqrt + eps));
         p[j] = pj; m[j] = mj; v[j] = vj;
-        if (sh) {
-          if (sh_dtype == SMOE_F16) reinterpret_cast<f16*>(sh)[j] = (f16)pj;
-          else reinterpret_cast<bf16_bits*>(sh)[j] = f32_to_bf16(pj);
-        }
+        image_store1(sh, sh_dtype, j, pj);
       }
     }
   }
@@ -163,16 +138,12 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_multi_kernel(const int64_t*
                                                                   const float* __restrict__ found_inf,
                                                                   const int64_t* __restrict__ shadow) {
   if (found_inf && *found_inf != 0.f) return;
-  const int t = blk[blockIdx.x];
-  if (t < 0 || t >= n_t) return;
-  const int64_t n = tab[4ll * n_t + t];
-  const int64_t base = (int64_t)blk[n_blocks + blockIdx.x] * SUMSQ_BLOCK;
-  const int64_t end = base + SUMSQ_BLOCK < n ? base + SUMSQ_BLOCK : n;
-  adamw_range<GT>(reinterpret_cast<float*>(tab[t]), reinterpret_cast<const GT*>(tab[(int64_t)n_t + t]),
-                  reinterpret_cast<float*>(tab[2ll * n_t + t]), reinterpret_cast<float*>(tab[3ll * n_t + t]),
-                  base + threadIdx.x * 4, end, OPT_THREADS * 4, n, hyp[t], b1, b2, eps, hyp[n_t + t], *step,
-                  grad_mult ? *grad_mult : 1.0f, shadow ? reinterpret_cast<void*>(shadow[t]) : nullptr,
-                  shadow ? (int)shadow[(int64_t)n_t + t] : SMOE_F16);
+  int t;
+  if (!opt_tensor(blk, n_t, t)) return;
+  const int64_t n = opt_entry<4>(tab, n_t, t), base = opt_base(blk, n_blocks);
+  adamw_range<GT>(opt_row<float, 0>(tab, n_t, t), opt_row<const GT, 1>(tab, n_t, t), opt_row<float, 2>(tab, n_t, t),
+                  opt_row<float, 3>(tab, n_t, t), base + threadIdx.x * 4, opt_end(base, n), OPT_THREADS * 4, n, hyp[t], b1, b2, eps,
+                  hyp[n_t + t], *step, grad_mult ? *grad_mult : 1.0f, opt_image(shadow, t), opt_image_dtype(shadow, n_t, t));
 }
 
 // weight EMA (timm.utils.ModelEma.update: `ema_v.copy_(ema_v * decay + (1. - decay) * model_v)`, engine.py:77-78), in place.
@@ -184,16 +155,15 @@ __global__ __launch_bounds__(OPT_THREADS) void ema_update_multi_kernel(const int
                                                                        float decay, float one_minus_decay,
                                                                        const float* __restrict__ skip) {
   if (skip && *skip != 0.f) return;
-  const int t = blk[blockIdx.x];
-  if (t < 0 || t >= n_t) return;   // the table is caller data
-  float* __restrict__ e = reinterpret_cast<float*>(tab[t]);
-  const float* __restrict__ m = reinterpret_cast<const float*>(tab[(int64_t)n_t + t]);
-  const int64_t n = tab[2ll * n_t + t];
-  const int64_t base = (int64_t)blk[n_blocks + blockIdx.x] * SUMSQ_BLOCK;
-  if (base + SUMSQ_BLOCK <= n) {
+  int t;
+  if (!opt_tensor(blk, n_t, t)) return;
+  float* __restrict__ e = opt_row<float, 0>(tab, n_t, t);
+  const float* __restrict__ m = opt_row<const float, 1>(tab, n_t, t);
+  const int64_t n = opt_entry<2>(tab, n_t, t), base = opt_base(blk, n_blocks);
+  if (base + OPT_BLOCK <= n) {
     // a whole block: 16 x 16 bytes of each tensor per thread, loads issued EMA_UNROLL vectors at a time (more bytes in flight)
     constexpr int EMA_UNROLL = 4;
-    for (int k = 0; k < SUMSQ_BLOCK / (OPT_THREADS * 4); k += EMA_UNROLL) {
+    for (int k = 0; k < OPT_BLOCK / (OPT_THREADS * 4); k += EMA_UNROLL) {
       f32x4 ev[EMA_UNROLL], mv[EMA_UNROLL];
 #pragma unroll
       for (int u = 0; u < EMA_UNROLL; ++u) {
@@ -245,7 +215,7 @@ __global__ void step_advance_kernel(float* step, const float* found_inf) {
 
 }  // namespace
 
-extern "C" int64_t smoe_grad_sumsq_blocks(int64_t n) { return n > 0 ? (n + SUMSQ_BLOCK - 1) / SUMSQ_BLOCK : 0; }
+extern "C" int64_t smoe_grad_sumsq_blocks(int64_t n) { return n > 0 ? (n + OPT_BLOCK - 1) / OPT_BLOCK : 0; }
 
 extern "C" int smoe_grad_sumsq(const void* g, int g_dtype, int64_t n, const float* inv_scale, float* partial, float* found_inf,
                                void* stream) {
@@ -254,11 +224,10 @@ extern "C" int smoe_grad_sumsq(const void* g, int g_dtype, int64_t n, const floa
   SMOE_REQUIRE(g && partial, "smoe_grad_sumsq: null pointer");
   const int grid = (int)smoe_grad_sumsq_blocks(n);
   hipStream_t s = (hipStream_t)stream;
-  switch (g_dtype) {
-    case SMOE_F32: hipLaunchKernelGGL(grad_sumsq_kernel<float>, dim3(grid), dim3(OPT_THREADS), 0, s, (const float*)g, n, inv_scale, partial, found_inf); break;
-    case SMOE_F16: hipLaunchKernelGGL(grad_sumsq_kernel<f16>, dim3(grid), dim3(OPT_THREADS), 0, s, (const f16*)g, n, inv_scale, partial, found_inf); break;
-    default: hipLaunchKernelGGL(grad_sumsq_kernel<bf16_bits>, dim3(grid), dim3(OPT_THREADS), 0, s, (const bf16_bits*)g, n, inv_scale, partial, found_inf); break;
-  }
+  opt_dispatch_grad(g_dtype, [&](auto tag) {
+    using GT = typename decltype(tag)::T;
+    hipLaunchKernelGGL(grad_sumsq_kernel<GT>, dim3(grid), dim3(OPT_THREADS), 0, s, (const GT*)g, n, inv_scale, partial, found_inf);
+  });
   SMOE_CHECK_LAUNCH("smoe_grad_sumsq");
   return 0;
 }
@@ -273,11 +242,11 @@ extern "C" int smoe_adamw_step(float* p, const void* g, int g_dtype, float* m, f
   if (blocks < 1) blocks = 1;
   if (blocks > 16384) blocks = 16384;
   hipStream_t s = (hipStream_t)stream;
-  switch (g_dtype) {
-    case SMOE_F32: hipLaunchKernelGGL(adamw_kernel<float>, dim3((int)blocks), dim3(OPT_THREADS), 0, s, p, (const float*)g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_mult, found_inf); break;
-    case SMOE_F16: hipLaunchKernelGGL(adamw_kernel<f16>, dim3((int)blocks), dim3(OPT_THREADS), 0, s, p, (const f16*)g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_mult, found_inf); break;
-    default: hipLaunchKernelGGL(adamw_kernel<bf16_bits>, dim3((int)blocks), dim3(OPT_THREADS), 0, s, p, (const bf16_bits*)g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_mult, found_inf); break;
-  }
+  opt_dispatch_grad(g_dtype, [&](auto tag) {
+    using GT = typename decltype(tag)::T;
+    hipLaunchKernelGGL(adamw_kernel<GT>, dim3((int)blocks), dim3(OPT_THREADS), 0, s, p, (const GT*)g, m, v, n, lr, beta1, beta2, eps,
+                       weight_decay, step, grad_mult, found_inf);
+  });
   SMOE_CHECK_LAUNCH("smoe_adamw_step");
   return 0;
 }
@@ -300,16 +269,13 @@ extern "C" int smoe_step_advance(float* step, const float* found_inf, void* stre
 
 extern "C" int smoe_grad_sumsq_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, int g_dtype,
                                      const float* inv_scale, float* partial, float* found_inf, void* stream) {
-  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31) && smoe_dtype_ok(g_dtype), "smoe_grad_sumsq_multi: bad arguments");
+  SMOE_REQUIRE(opt_multi_ok(n_tensors, n_blocks, g_dtype), "smoe_grad_sumsq_multi: bad arguments");
   if (n_blocks == 0) return 0;
   SMOE_REQUIRE(tab && blk && partial, "smoe_grad_sumsq_multi: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)n_blocks), block(OPT_THREADS);
-  switch (g_dtype) {
-    case SMOE_F32: hipLaunchKernelGGL(grad_sumsq_multi_kernel<float>, grid, block, 0, s, tab, n_tensors, blk, n_blocks, inv_scale, partial, found_inf); break;
-    case SMOE_F16: hipLaunchKernelGGL(grad_sumsq_multi_kernel<f16>, grid, block, 0, s, tab, n_tensors, blk, n_blocks, inv_scale, partial, found_inf); break;
-    default: hipLaunchKernelGGL(grad_sumsq_multi_kernel<bf16_bits>, grid, block, 0, s, tab, n_tensors, blk, n_blocks, inv_scale, partial, found_inf); break;
-  }
+  opt_dispatch_grad(g_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(grad_sumsq_multi_kernel<typename decltype(tag)::T>, dim3((unsigned)n_blocks), dim3(OPT_THREADS), 0,
+                       (hipStream_t)stream, tab, n_tensors, blk, n_blocks, inv_scale, partial, found_inf);
+  });
   SMOE_CHECK_LAUNCH("smoe_grad_sumsq_multi");
   return 0;
 }
@@ -317,23 +283,20 @@ extern "C" int smoe_grad_sumsq_multi(const int64_t* tab, int n_tensors, const in
 extern "C" int smoe_adamw_step_multi(const int64_t* tab, const float* hyp, int n_tensors, const int32_t* blk, int64_t n_blocks,
                                      int g_dtype, double beta1, double beta2, float eps, const float* step, const float* grad_mult,
                                      const float* found_inf, const int64_t* shadow, void* stream) {
-  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31) && smoe_dtype_ok(g_dtype), "smoe_adamw_step_multi: bad arguments");
+  SMOE_REQUIRE(opt_multi_ok(n_tensors, n_blocks, g_dtype), "smoe_adamw_step_multi: bad arguments");
   if (n_blocks == 0) return 0;
   SMOE_REQUIRE(tab && hyp && blk && step, "smoe_adamw_step_multi: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)n_blocks), block(OPT_THREADS);
-  switch (g_dtype) {
-    case SMOE_F32: hipLaunchKernelGGL(adamw_multi_kernel<float>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, eps, step, grad_mult, found_inf, shadow); break;
-    case SMOE_F16: hipLaunchKernelGGL(adamw_multi_kernel<f16>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, eps, step, grad_mult, found_inf, shadow); break;
-    default: hipLaunchKernelGGL(adamw_multi_kernel<bf16_bits>, grid, block, 0, s, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, eps, step, grad_mult, found_inf, shadow); break;
-  }
+  opt_dispatch_grad(g_dtype, [&](auto tag) {
+    hipLaunchKernelGGL(adamw_multi_kernel<typename decltype(tag)::T>, dim3((unsigned)n_blocks), dim3(OPT_THREADS), 0,
+                       (hipStream_t)stream, tab, hyp, n_tensors, blk, n_blocks, beta1, beta2, eps, step, grad_mult, found_inf, shadow);
+  });
   SMOE_CHECK_LAUNCH("smoe_adamw_step_multi");
   return 0;
 }
 
 extern "C" int smoe_ema_update_multi(const int64_t* tab, int n_tensors, const int32_t* blk, int64_t n_blocks, float decay,
                                      float one_minus_decay, const float* skip, void* stream) {
-  SMOE_REQUIRE(n_tensors >= 0 && n_blocks >= 0 && n_blocks < (1ll << 31), "smoe_ema_update_multi: bad arguments");
+  SMOE_REQUIRE(opt_multi_ok(n_tensors, n_blocks), "smoe_ema_update_multi: bad arguments");
   if (n_blocks == 0) return 0;
   SMOE_REQUIRE(tab && blk, "smoe_ema_update_multi: null pointer");
   hipLaunchKernelGGL(ema_update_multi_kernel, dim3((unsigned)n_blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, tab, n_tensors,

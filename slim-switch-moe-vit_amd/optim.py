@@ -27,7 +27,7 @@ timm's line and skippable from the device, so that the graphed training step can
 """
 from __future__ import annotations
 
-from typing import Iterable, Optional
+from typing import Iterable, NamedTuple, Optional
 
 import torch
 
@@ -44,14 +44,15 @@ def _hip_ok(p: torch.Tensor) -> bool:
     return p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
 
 
-SUMSQ_BLOCK = 16384   # elements per workgroup of the multi-tensor kernels (csrc/optim.hip)
-_blk_cache = {}       # (device, numels) -> (blk int32 [2, n_blocks] on the device, blocks per tensor)
+SUMSQ_BLOCK = 16384   # elements per workgroup of every multi-tensor kernel: OPT_BLOCK of csrc/optim_table.h
+_size_cache = {}      # (device, numels) -> [blk, nb, first]: what the multi-tensor launches need that depends on the tensor sizes only
 
 
-def _block_table(numels, device):
-    """Workgroup -> (tensor, 16K-element block) map of the multi-tensor kernels; depends on the tensor sizes only, cached."""
+def _size_tables(numels, device):
+    """The cache entry of these tensor sizes: blk = int32 [2, n_blocks] on the device (tensor of workgroup b, 16K-element block inside
+    it), nb = blocks per tensor, first = None until ``_first_block_table`` asks for it."""
     key = (str(device), tuple(numels))
-    hit = _blk_cache.get(key)
+    hit = _size_cache.get(key)
     if hit is None:
         import numpy as np
         nb = [(n + SUMSQ_BLOCK - 1) // SUMSQ_BLOCK for n in numels]
@@ -59,10 +60,24 @@ def _block_table(numels, device):
         first = np.cumsum([0] + nb[:-1]) if nb else np.zeros(0, dtype=np.int64)
         index = (np.arange(int(sum(nb)), dtype=np.int64) - np.repeat(first, nb)).astype(np.int32)
         blk = torch.from_numpy(np.stack([tens, index]) if len(tens) else np.zeros((2, 0), dtype=np.int32)).to(device)
-        if len(_blk_cache) > 16:
-            _blk_cache.clear()
-        hit = _blk_cache[key] = (blk.contiguous(), nb)
+        if len(_size_cache) > 16:
+            _size_cache.clear()
+        hit = _size_cache[key] = [blk.contiguous(), nb, None]
     return hit
+
+
+def _block_table(numels, device):
+    """Workgroup -> (tensor, 16K-element block) map of the multi-tensor kernels and the blocks per tensor; cached."""
+    return tuple(_size_tables(numels, device)[:2])
+
+
+def _first_block_table(numels, device):
+    """int32 [n_t + 1] on the device: first 16K-element block of every tensor in ``_block_table``'s order, the block count at the end
+    (what smoe_lamb_trust_multi walks a tensor's block partials by).  The same cache entry."""
+    hit = _size_tables(numels, device)
+    if hit[2] is None:
+        hit[2] = torch.tensor([sum(hit[1][:t]) for t in range(len(hit[1]) + 1)], dtype=torch.int32).to(device)
+    return hit[2]
 
 
 _staging = []          # pinned staging buffers of tables copied to the device while a HIP graph was being captured: kept for good
@@ -90,6 +105,55 @@ def _host_table(rows, dtype, device):
 def _pointer_table(rows, device):
     """int64 [len(rows), n_t] on the device (addresses and element counts)."""
     return _host_table(rows, torch.int64, device)
+
+
+class _Item(NamedTuple):
+    # one parameter of a fused step: its group (lr, weight decay, ...), the parameter, its gradient and its two moments
+    group: dict
+    p: torch.Tensor
+    g: torch.Tensor
+    exp_avg: torch.Tensor
+    exp_avg_sq: torch.Tensor
+
+
+def _closure_loss(closure):
+    with torch.enable_grad():
+        return closure() if closure is not None else None
+
+
+def _moment_state(state, p, with_step: bool):
+    """state[p] with exp_avg / exp_avg_sq made at the parameter's first step (``with_step``: and torch.optim.AdamW's ``step`` = 0)."""
+    st = state[p]
+    if not st:
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if with_step:
+            st["step"] = 0
+    return st
+
+
+def _step_tables(items, hyp_rows, dev):
+    """One multi-tensor step launch's tab int64 [5][n_t] (p, g, exp_avg, exp_avg_sq addresses and n), hyp f32 [len(hyp_rows)][n_t] and
+    shadow table int64 [2][n_t] (address / dtype of every 16-bit operand image that is current NOW, None without any: the kernel writes
+    them in the same pass, so no cast pass over every weight follows the step), and the images to stamp: [(p, (cache, key, image))]."""
+    tab = _pointer_table([[it.p.data_ptr() for it in items], [it.g.data_ptr() for it in items], [it.exp_avg.data_ptr() for it in items],
+                          [it.exp_avg_sq.data_ptr() for it in items], [it.p.numel() for it in items]], dev)
+    hyp = _host_table(hyp_rows, torch.float32, dev)
+    shadows = [shadow_of(it.p) if SHADOW_STEP else None for it in items]
+    sh_tab = None
+    if any(sh is not None for sh in shadows):
+        sh_tab = _pointer_table([[sh[2].data_ptr() if sh is not None else 0 for sh in shadows],
+                                 [ops.dtype_code(sh[2].dtype) if sh is not None else 0 for sh in shadows]], dev)
+    return tab, hyp, sh_tab, [(it.p, sh) for it, sh in zip(items, shadows) if sh is not None]
+
+
+def _finish_step(params, images) -> None:
+    """The kernels wrote the parameters through raw pointers: autograd's version counters did not move, and every derived tensor keyed
+    on them (16-bit weight shadows, zero-row constants) would go on serving the OLD weights.  Bump the versions, as an in-place torch
+    op would have; the images the step wrote itself belong to the NEW version of their parameter."""
+    _bump_versions(params)
+    for p, (cache, key, img) in images:
+        cache.refresh(key, img, param_version(p))
 
 
 class AdamW(torch.optim.Optimizer):
@@ -150,28 +214,20 @@ class AdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, grad_mult: Optional[torch.Tensor] = None, found_inf: Optional[torch.Tensor] = None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = None
+        loss = _closure_loss(closure)
         advanced = set()
-        refreshed = []   # [(parameter, (cache, key, image))]: 16-bit images the fused step wrote
-        batches = {}   # (device, grad dtype, betas, eps) -> [(p, g, exp_avg, exp_avg_sq, lr, wd)]: one launch each
+        images = []    # [(parameter, (cache, key, image))]: 16-bit images the fused step wrote
+        batches = {}   # (device, grad dtype, betas, eps) -> [_Item]: one launch each
         for group in self.param_groups:
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                st = self.state[p]
-                if not st:
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["step"] = 0
+                st = _moment_state(self.state, p, with_step=True)
                 g = p.grad
                 if _hip_ok(p) and g.is_cuda and g.is_contiguous() and g.dtype in ops._DT:
                     batches.setdefault((p.device, g.dtype, float(b1), float(b2), float(eps)), []).append(
-                        (p, g, st["exp_avg"], st["exp_avg_sq"], float(lr), float(wd)))
+                        _Item(group, p, g, st["exp_avg"], st["exp_avg_sq"]))
                 else:                 # torch composition (CPU tensors, other dtypes): same arithmetic
                     if found_inf is not None and float(found_inf) != 0.0:
                         continue
@@ -183,45 +239,30 @@ class AdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"].mul_(b2).addcmul_(gg, gg, value=1 - b2)
                     denom = (st["exp_avg_sq"].sqrt() / (1 - b2 ** t) ** 0.5).add_(eps)
                     p.addcdiv_(st["exp_avg"], denom, value=-lr / (1 - b1 ** t))
+        lib = _lib.load() if batches else None
         for (dev, gdt, b1, b2, eps), items in batches.items():
-            if lib is None:
-                lib = _lib.load()
+            lrs, wds = [float(it.group["lr"]) for it in items], [float(it.group["weight_decay"]) for it in items]
             step_t = self._step_counter(dev)
-            stream = ops._stream(items[0][0])
+            stream = ops._stream(items[0].p)
             if dev not in advanced:   # one counter per device: every parameter of a step sees the same t
                 _lib.check(lib.smoe_step_advance(step_t.data_ptr(), ops._ptr(found_inf), stream), "smoe_step_advance")
                 advanced.add(dev)
             if len(items) == 1:
-                p, g, m, v, lr, wd = items[0]
-                rc = lib.smoe_adamw_step(p.data_ptr(), g.data_ptr(), ops.dtype_code(gdt), m.data_ptr(), v.data_ptr(), p.numel(),
-                                         lr, b1, b2, eps, wd, step_t.data_ptr(), ops._ptr(grad_mult), ops._ptr(found_inf), stream)
+                it = items[0]
+                rc = lib.smoe_adamw_step(it.p.data_ptr(), it.g.data_ptr(), ops.dtype_code(gdt), it.exp_avg.data_ptr(),
+                                         it.exp_avg_sq.data_ptr(), it.p.numel(), lrs[0], b1, b2, eps, wds[0], step_t.data_ptr(),
+                                         ops._ptr(grad_mult), ops._ptr(found_inf), stream)
                 _lib.check(rc, "smoe_adamw_step")
                 continue
             # every tensor of the batch in ONE launch (a ViT-B/16 MoE has ~180 parameter tensors)
-            blk, nb = _block_table([it[0].numel() for it in items], dev)
-            tab = _pointer_table([[it[0].data_ptr() for it in items], [it[1].data_ptr() for it in items],
-                                  [it[2].data_ptr() for it in items], [it[3].data_ptr() for it in items],
-                                  [it[0].numel() for it in items]], dev)
-            hyp = _host_table([[it[4] for it in items], [it[5] for it in items]], torch.float32, dev)
-            # 16-bit operand images of the parameters that are current NOW (the modules' weight shadows): written in the same pass,
-            # so the next forward finds them current (no f32 -> 16-bit cast pass over every weight per step)
-            shadows = [shadow_of(it[0]) if SHADOW_STEP else None for it in items]
-            sh_tab = None
-            if any(sh is not None for sh in shadows):
-                sh_tab = _pointer_table([[sh[2].data_ptr() if sh is not None else 0 for sh in shadows],
-                                         [ops.dtype_code(sh[2].dtype) if sh is not None else 0 for sh in shadows]], dev)
+            blk, nb = _block_table([it.p.numel() for it in items], dev)
+            tab, hyp, sh_tab, written = _step_tables(items, [lrs, wds], dev)
             rc = lib.smoe_adamw_step_multi(tab.data_ptr(), hyp.data_ptr(), len(items), blk.data_ptr(), sum(nb), ops.dtype_code(gdt),
                                            b1, b2, eps, step_t.data_ptr(), ops._ptr(grad_mult), ops._ptr(found_inf), ops._ptr(sh_tab),
                                            stream)
             _lib.check(rc, "smoe_adamw_step_multi")
-            refreshed.extend((it[0], sh) for it, sh in zip(items, shadows) if sh is not None)
-        # The kernels wrote the parameters through raw pointers: autograd's version counters did not move, and every derived
-        # tensor keyed on them (the 16-bit weight shadows of the expert GEMMs and of the dense projections, the zero-row
-        # constants) would go on serving the OLD weights.  Bump the versions, as an in-place torch op would have.
-        for items in batches.values():
-            _bump_versions([it[0] for it in items])
-        for p, (cache, key, img) in refreshed:        # the images written above belong to the NEW version of their parameter
-            cache.refresh(key, img, param_version(p))
+            images.extend(written)
+        _finish_step([it.p for items in batches.values() for it in items], images)
         return loss
 
 
@@ -241,42 +282,31 @@ def _bump_versions(tensors) -> None:
         invalidate_all()
 
 
-_first_cache = {}     # (device, numels) -> int32 [n_t + 1] on the device: first block of every tensor in _block_table's order
-
-
-def _first_block_table(numels, device):
-    """First 16K-element block of every tensor (and the block count at the end): what smoe_lamb_trust_multi walks a tensor's block
-    partials by.  Depends on the tensor sizes only, cached next to ``_block_table``."""
-    key = (str(device), tuple(numels))
-    hit = _first_cache.get(key)
-    if hit is None:
-        first = [0]
-        for n in numels:
-            first.append(first[-1] + (n + SUMSQ_BLOCK - 1) // SUMSQ_BLOCK)
-        if len(_first_cache) > 16:
-            _first_cache.clear()
-        hit = _first_cache[key] = torch.tensor(first, dtype=torch.int32).to(device)
-    return hit
-
-
-def _grad_sumsq_partials(grads, mul, found_inf, device):
-    """One ``smoe_grad_sumsq_multi`` launch per gradient dtype over ``grads`` (non-empty device tensors): the list of block-partial
-    tensors of sum((g * *mul)^2), ``mul`` / ``found_inf`` optional device f32[1]."""
+def _grad_sumsq_launch(grads, mul, found_inf, device):
+    """One ``smoe_grad_sumsq_multi`` launch per gradient dtype over the non-empty device tensors ``grads``: per dtype, ``(partials,
+    gradients in launch order, blocks per gradient)``, partials = the 16K-element block sums of (g * *mul)^2; ``mul`` / ``found_inf``: f32[1] or None."""
     lib = _lib.load()
     by_dtype = {}
     for g in grads:
-        by_dtype.setdefault(g.dtype, []).append(g)
-    partials = []
+        if g.numel():
+            by_dtype.setdefault(g.dtype, []).append(g)
+    out = []
     for gdt, gs in by_dtype.items():
-        blk, nb = _block_table([g.numel() for g in gs], device)
+        numels = [g.numel() for g in gs]
+        blk, nb = _block_table(numels, device)
         zeros = [0] * len(gs)
-        tab = _pointer_table([zeros, [g.data_ptr() for g in gs], zeros, zeros, [g.numel() for g in gs]], device)
+        tab = _pointer_table([zeros, [g.data_ptr() for g in gs], zeros, zeros, numels], device)
         part = torch.empty(sum(nb), dtype=torch.float32, device=device)
         rc = lib.smoe_grad_sumsq_multi(tab.data_ptr(), len(gs), blk.data_ptr(), sum(nb), ops.dtype_code(gdt), ops._ptr(mul),
                                        part.data_ptr(), ops._ptr(found_inf), ops._stream(part))
         _lib.check(rc, "smoe_grad_sumsq_multi")
-        partials.append(part)
-    return partials
+        out.append((part, gs, nb))
+    return out
+
+
+def _grad_sumsq_partials(grads, mul, found_inf, device):
+    # (the block partials alone, one tensor per gradient dtype)
+    return [part for part, _, _ in _grad_sumsq_launch(grads, mul, found_inf, device)]
 
 
 class Lamb(torch.optim.Optimizer):
@@ -380,27 +410,21 @@ class Lamb(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, grad_mult: Optional[torch.Tensor] = None, found_inf: Optional[torch.Tensor] = None,
              grad_sumsq=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        entries = []      # (group, p, g, exp_avg, exp_avg_sq) of every non-empty parameter with a gradient
+        loss = _closure_loss(closure)
+        entries = []      # _Item of every non-empty parameter with a gradient
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if p.grad.is_sparse:
                     raise RuntimeError("Lamb does not support sparse gradients, consider SparseAdam instead.")
-                st = self.state[p]
-                if not st:
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st = _moment_state(self.state, p, with_step=False)
                 if p.numel():
-                    entries.append((group, p, p.grad, st["exp_avg"], st["exp_avg_sq"]))
+                    entries.append(_Item(group, p, p.grad, st["exp_avg"], st["exp_avg_sq"]))
         if not entries:
             return loss
-        dev = entries[0][1].device
-        if all(p.device == dev and self._fusable(p, g, m, v) for _, p, g, m, v in entries):
+        dev = entries[0].p.device
+        if all(it.p.device == dev and self._fusable(it.p, it.g, it.exp_avg, it.exp_avg_sq) for it in entries):
             self._fused_step(entries, dev, grad_mult, found_inf, grad_sumsq)
         else:
             self._torch_step(entries, grad_mult, found_inf)
@@ -415,7 +439,7 @@ class Lamb(torch.optim.Optimizer):
         if found_inf is not None and float(found_inf) != 0.0:
             return
         gm = float(grad_mult) if grad_mult is not None else 1.0
-        grads = [g.float() * gm for _, _, g, _, _ in entries]
+        grads = [it.g.float() * gm for it in entries]
         G = math.sqrt(sum(float(gg.pow(2).sum()) for gg in grads))
         mgn = self.defaults["max_grad_norm"]
         clip = G / mgn if (mgn is not None and G > mgn) else 1.0
@@ -458,13 +482,13 @@ class Lamb(torch.optim.Optimizer):
 
     def _fused_step(self, entries, dev, grad_mult, found_inf, grad_sumsq) -> None:
         lib = _lib.load()
-        stream = ops._stream(entries[0][1])
+        stream = ops._stream(entries[0].p)
         step_t = self._step_counter(dev)
         # G and the clip factor, from the norm pass's block partials (the scaler's, or a pass of this step's own)
         if grad_sumsq is not None:
             partials, num, den = list(grad_sumsq[0]), grad_mult, grad_sumsq[1]
         else:
-            partials, num, den = _grad_sumsq_partials([g for _, _, g, _, _ in entries], grad_mult, None, dev), None, None
+            partials, num, den = _grad_sumsq_partials([it.g for it in entries], grad_mult, None, dev), None, None
         part = partials[0] if len(partials) == 1 else torch.cat(partials)
         out = self._norm_dev.get(dev)
         if out is None:
@@ -476,28 +500,22 @@ class Lamb(torch.optim.Optimizer):
         self.last_grad_norm = out
         _lib.check(lib.smoe_step_advance(step_t.data_ptr(), ops._ptr(found_inf), stream), "smoe_step_advance")
         batches = {}      # (grad dtype, betas, eps, bias_correction, grad_averaging, trust_clip) -> entries: four launches each
-        for ent in entries:
-            group, g = ent[0], ent[2]
+        for it in entries:
+            group = it.group
             b1, b2 = group["betas"]
-            batches.setdefault((g.dtype, float(b1), float(b2), float(group["eps"]), bool(group["bias_correction"]),
-                                bool(group["grad_averaging"]), bool(group["trust_clip"])), []).append(ent)
-        refreshed = []
+            batches.setdefault((it.g.dtype, float(b1), float(b2), float(group["eps"]), bool(group["bias_correction"]),
+                                bool(group["grad_averaging"]), bool(group["trust_clip"])), []).append(it)
+        images = []
         self._trust = []
         for (gdt, b1, b2, eps, bias, averaging, trust_clip), items in batches.items():
-            numels = [p.numel() for _, p, _, _, _ in items]
+            numels = [it.p.numel() for it in items]
             blk, nb = _block_table(numels, dev)
             first = _first_block_table(numels, dev)
             n_blocks = sum(nb)
-            tab = _pointer_table([[p.data_ptr() for _, p, _, _, _ in items], [g.data_ptr() for _, _, g, _, _ in items],
-                                  [m.data_ptr() for _, _, _, m, _ in items], [v.data_ptr() for _, _, _, _, v in items], numels], dev)
-            hyp = _host_table([[float(gr["lr"]) for gr, _, _, _, _ in items], [float(gr["weight_decay"]) for gr, _, _, _, _ in items],
-                               [1.0 if (gr["weight_decay"] != 0 or gr["always_adapt"]) else 0.0 for gr, _, _, _, _ in items]],
-                              torch.float32, dev)
-            shadows = [shadow_of(p) if SHADOW_STEP else None for _, p, _, _, _ in items]
-            sh_tab = None
-            if any(sh is not None for sh in shadows):
-                sh_tab = _pointer_table([[sh[2].data_ptr() if sh is not None else 0 for sh in shadows],
-                                         [ops.dtype_code(sh[2].dtype) if sh is not None else 0 for sh in shadows]], dev)
+            groups = [it.group for it in items]
+            tab, hyp, sh_tab, written = _step_tables(
+                items, [[float(gr["lr"]) for gr in groups], [float(gr["weight_decay"]) for gr in groups],
+                        [1.0 if (gr["weight_decay"] != 0 or gr["always_adapt"]) else 0.0 for gr in groups]], dev)
             norms = torch.empty((2, n_blocks), dtype=torch.float32, device=dev)
             trust = torch.ones(len(items), dtype=torch.float32, device=dev)
             rc = lib.smoe_lamb_stage1_multi(tab.data_ptr(), hyp.data_ptr(), len(items), blk.data_ptr(), n_blocks, ops.dtype_code(gdt),
@@ -510,12 +528,9 @@ class Lamb(torch.optim.Optimizer):
             rc = lib.smoe_lamb_stage2_multi(tab.data_ptr(), hyp.data_ptr(), len(items), blk.data_ptr(), n_blocks, b1, b2, eps, int(bias),
                                             step_t.data_ptr(), trust.data_ptr(), ops._ptr(found_inf), ops._ptr(sh_tab), stream)
             _lib.check(rc, "smoe_lamb_stage2_multi")
-            self._trust.append(([p for _, p, _, _, _ in items], trust))
-            refreshed.extend((it[1], sh) for it, sh in zip(items, shadows) if sh is not None)
-        # the kernels wrote through raw pointers: move the version counters (AdamW.step), then stamp the images written above
-        _bump_versions([p for _, p, _, _, _ in entries])
-        for p, (cache, key, img) in refreshed:
-            cache.refresh(key, img, param_version(p))
+            self._trust.append(([it.p for it in items], trust))
+            images.extend(written)
+        _finish_step([it.p for it in entries], images)
 
 
 def _foreign_step_hook(optimizer, args, kwargs) -> None:
@@ -627,25 +642,13 @@ class NativeScaler:
         if clip_grad is not None:
             assert parameters is not None, "clip_grad needs `parameters` (timm NativeScaler)"
         # pass 1 over every gradient the optimizer will use: non-finite check (+ the norm's partial sums where clipped)
-        grads = [p.grad for p in params]
-        clip_ids = {id(p) for p in clip_over if p.grad is not None} if clip_over is not None else set()
-        # one launch per gradient dtype over every gradient (partials in parameter order, 16K-element blocks)
-        by_dtype = {}
-        for p, g in zip(params, grads):
-            if g.numel():
-                by_dtype.setdefault(g.dtype, []).append((p, g))
+        # (one launch per gradient dtype over every gradient: partials in parameter order, 16K-element blocks)
+        clipped = {id(p.grad) for p in clip_over if p.grad is not None} if clip_over is not None else set()
         partials, masks = [], []
-        for gdt, items in by_dtype.items():
-            blk, nb = _block_table([g.numel() for _, g in items], dev)
-            zeros = [0] * len(items)
-            tab = _pointer_table([zeros, [g.data_ptr() for _, g in items], zeros, zeros, [g.numel() for _, g in items]], dev)
-            part = torch.empty(sum(nb), dtype=torch.float32, device=dev)
-            rc = lib.smoe_grad_sumsq_multi(tab.data_ptr(), len(items), blk.data_ptr(), sum(nb), ops.dtype_code(gdt),
-                                           inv_scale.data_ptr(), part.data_ptr(), found_inf.data_ptr(), ops._stream(part))
-            _lib.check(rc, "smoe_grad_sumsq_multi")
+        for part, gs, nb in _grad_sumsq_launch([p.grad for p in params], inv_scale, found_inf, dev):
             partials.append(part)
             if clip_grad is not None:
-                masks.append(self._clip_mask([id(p) in clip_ids for p, _ in items], nb, dev))
+                masks.append(self._clip_mask([id(g) in clipped for g in gs], nb, dev))
         mult = inv_scale
         if clip_grad is not None:
             total = torch.zeros((), dtype=torch.float32, device=dev)

@@ -302,3 +302,64 @@ def test_lamb_checkpoint_round_trip_in_timms_layout():
         o.step()
     assert all(torch.equal(a.detach(), b.detach()) for a, b in zip(params, again))
     assert float(opt2._step_counter(torch.device(DEV))) == float(cases.STEPS + 1)
+
+
+IMAGE_NUMELS = [3, 5, 16385]      # the scalar tail alone; one 16-byte vector and a tail; a second block
+NAN16 = 0x7FA5                    # a NaN in f16 and in bf16: what an image holds before a step writes it
+
+
+def _image_step(kind, img_dt, found):
+    """One fused step of `kind` ("adamw": smoe_adamw_step_multi; "lamb": stage 1, trust ratios, stage 2) over three tensors from the
+    same seeded state, every tensor with a 16-bit image of `img_dt`, found_inf = `found`: (p before, p after, images)."""
+    from slim_switch_moe_vit_amd import _lib, ops, optim
+    lib, dev = _lib.load(), torch.device(DEV)
+    gen = torch.Generator().manual_seed(7)
+    p0 = [torch.randn(n, generator=gen) * 0.5 for n in IMAGE_NUMELS]
+    ps = [t.clone().to(DEV) for t in p0]
+    gs = [(torch.randn(n, generator=gen) * 1e-2).half().to(DEV) for n in IMAGE_NUMELS]
+    ms = [(torch.randn(n, generator=gen) * 1e-2).to(DEV) for n in IMAGE_NUMELS]
+    vs = [(torch.rand(n, generator=gen) * 1e-4).to(DEV) for n in IMAGE_NUMELS]
+    imgs = [torch.full((n,), NAN16, dtype=torch.int16, device=DEV) for n in IMAGE_NUMELS]
+    n_t = len(ps)
+    blk, nb = optim._block_table(IMAGE_NUMELS, dev)
+    tab = torch.tensor([[t.data_ptr() for t in ts] for ts in (ps, gs, ms, vs)] + [IMAGE_NUMELS], dtype=torch.int64, device=DEV)
+    shadow = torch.tensor([[t.data_ptr() for t in imgs], [ops.dtype_code(img_dt)] * n_t], dtype=torch.int64, device=DEV)
+    step = torch.tensor([3.0], device=DEV)
+    found_inf = torch.full((1,), float(found), device=DEV)
+    f16 = ops.dtype_code(torch.float16)
+    if kind == "adamw":
+        hyp = torch.tensor([[1e-2] * n_t, [0.05] * n_t], dtype=torch.float32, device=DEV)
+        rc = lib.smoe_adamw_step_multi(tab.data_ptr(), hyp.data_ptr(), n_t, blk.data_ptr(), sum(nb), f16, 0.9, 0.999, 1e-8,
+                                       step.data_ptr(), None, found_inf.data_ptr(), shadow.data_ptr(), None)
+        _lib.check(rc, "smoe_adamw_step_multi")
+    else:
+        hyp = torch.tensor([[1e-2] * n_t, [0.05] * n_t, [1.0] * n_t], dtype=torch.float32, device=DEV)
+        first = optim._first_block_table(IMAGE_NUMELS, dev)
+        norms = torch.zeros((2, sum(nb)), device=DEV)
+        trust = torch.ones(n_t, device=DEV)
+        rc = lib.smoe_lamb_stage1_multi(tab.data_ptr(), hyp.data_ptr(), n_t, blk.data_ptr(), sum(nb), f16, 0.9, 0.999, 0.1, 1e-6, 1,
+                                        step.data_ptr(), None, None, found_inf.data_ptr(), norms.data_ptr(), None)
+        _lib.check(rc, "smoe_lamb_stage1_multi")
+        rc = lib.smoe_lamb_trust_multi(norms.data_ptr(), sum(nb), first.data_ptr(), hyp.data_ptr(), n_t, 0, found_inf.data_ptr(),
+                                       trust.data_ptr(), None)
+        _lib.check(rc, "smoe_lamb_trust_multi")
+        rc = lib.smoe_lamb_stage2_multi(tab.data_ptr(), hyp.data_ptr(), n_t, blk.data_ptr(), sum(nb), 0.9, 0.999, 1e-6, 1,
+                                        step.data_ptr(), trust.data_ptr(), found_inf.data_ptr(), shadow.data_ptr(), None)
+        _lib.check(rc, "smoe_lamb_stage2_multi")
+    torch.cuda.synchronize()
+    return p0, ps, imgs
+
+
+@pytest.mark.parametrize("img_dt", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("kind", ["adamw", "lamb"])
+def test_the_16_bit_image_a_fused_step_writes_is_the_cast_of_the_new_weights_bitwise(kind, img_dt):
+    """AdamW's launch and LAMB's stage 2 write the image of every tensor through one store (csrc/optim_table.h): every element, in the
+    scalar tail, the vector body and a second block, is the round-to-nearest-even cast of the new f32 weight (finite values: torch's
+    `.to()` is that cast); a step skipped by found_inf leaves image and weights as they were."""
+    p0, ps, imgs = _image_step(kind, img_dt, 0)
+    for a, p, img in zip(p0, ps, imgs):
+        assert bool(torch.isfinite(p).all()) and not torch.equal(p.cpu(), a), "the step moved the weights"
+        assert torch.equal(img, p.to(img_dt).view(torch.int16)), (kind, img_dt, p.numel())
+    p0, ps, imgs = _image_step(kind, img_dt, 1)
+    for a, p, img in zip(p0, ps, imgs):
+        assert torch.equal(p.cpu(), a) and bool((img == NAN16).all()), (kind, img_dt, p.numel())

@@ -341,3 +341,41 @@ def test_training_harness_on_one_hip_graph_reproduces_the_eager_harness():
     fresh = fresh.to(DEV).eval()
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
         assert torch.equal(fresh(batches[0][0].to(DEV)).float(), l_g), "the weight images are current after the replays"
+
+
+@pytest.mark.parametrize("gdt", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+@pytest.mark.parametrize("n", [1, 7, 16384, 16385, 40003])
+def test_grad_sumsq_of_one_tensor_equals_its_blocks_in_a_three_tensor_launch_bitwise(n, gdt):
+    """"Same blocks, same arithmetic, same order of the partial sums" (csrc/optim.hip) for the norm pass: smoe_grad_sumsq on one
+    gradient and smoe_grad_sumsq_multi on a table that holds it between two others give the same block partials bit for bit and the
+    same found_inf, with a non-unit inv_scale, on finite values and with one inf in the last element."""
+    from slim_switch_moe_vit_amd import _lib, ops, optim
+    lib, dev = _lib.load(), torch.device(DEV)
+    gen = torch.Generator().manual_seed(n)
+    inv_scale = torch.full((1,), 0.37, device=DEV)
+    others = [torch.randn(5, generator=gen).to(gdt).to(DEV), torch.randn(16390, generator=gen).to(gdt).to(DEV)]
+    for poison in (False, True):
+        g = torch.randn(n, generator=gen)
+        if poison:
+            g[-1] = float("inf")
+        g = g.to(gdt).to(DEV)
+        nblocks = lib.smoe_grad_sumsq_blocks(n)
+        one, found_one = torch.empty(nblocks, device=DEV), torch.zeros(1, device=DEV)
+        rc = lib.smoe_grad_sumsq(g.data_ptr(), ops.dtype_code(gdt), n, inv_scale.data_ptr(), one.data_ptr(), found_one.data_ptr(), None)
+        _lib.check(rc, "smoe_grad_sumsq")
+        gs = [others[0], g, others[1]]
+        numels = [t.numel() for t in gs]
+        blk, nb = optim._block_table(numels, dev)
+        assert nb[1] == nblocks
+        zeros = [0] * 3
+        tab = torch.tensor([zeros, [t.data_ptr() for t in gs], zeros, zeros, numels], dtype=torch.int64, device=DEV)
+        multi, found_multi = torch.empty(sum(nb), device=DEV), torch.zeros(1, device=DEV)
+        rc = lib.smoe_grad_sumsq_multi(tab.data_ptr(), 3, blk.data_ptr(), sum(nb), ops.dtype_code(gdt), inv_scale.data_ptr(),
+                                       multi.data_ptr(), found_multi.data_ptr(), None)
+        _lib.check(rc, "smoe_grad_sumsq_multi")
+        torch.cuda.synchronize()
+        assert torch.equal(multi[nb[0]:nb[0] + nblocks].view(torch.int32), one.view(torch.int32)), (n, gdt, poison)
+        assert float(found_one) == float(found_multi) == (1.0 if poison else 0.0)
+        if not poison:      # (and they are the sum: f32 sums of non-negative terms, at most 64 + 6 + 2 additions deep, ~4.4e-6)
+            ref = float((g.double() * 0.37).pow(2).sum())
+            assert abs(float(one.double().sum()) - ref) <= 1e-5 * ref

@@ -356,6 +356,25 @@ def test_multi_tensor_block_table_and_wgrad_round_model():
     assert np.isclose(ops._wgrad_rounds(1, 256, 256, 256), 1.0)
 
 
+@pytest.mark.parametrize("numels", [[], [5], [5, 16384, 16385, 40000]], ids=str)
+def test_first_block_table_and_block_table_describe_the_same_blocks(numels):
+    """What smoe_lamb_trust_multi walks the block partials by (first) against what every multi-tensor kernel decodes its workgroup
+    from (blk), for no tensor, one tensor and sizes on either side of a 16K block: one layout, and both come out of a cache."""
+    from slim_switch_moe_vit_amd import optim as smo
+
+    blk, nb = smo._block_table(numels, "cpu")
+    first = smo._first_block_table(numels, "cpu")
+    assert nb == [-(-n // 16384) for n in numels]
+    assert first.dtype == torch.int32 and first.tolist() == [sum(nb[:t]) for t in range(len(nb))] + [sum(nb)]
+    assert blk.shape == (2, sum(nb)) and blk.dtype == torch.int32
+    assert blk[0].tolist() == [t for t, k in enumerate(nb) for _ in range(k)]          # tensor t, nb[t] times
+    assert blk[1].tolist() == [j for k in nb for j in range(k)]                        # restarts at 0 at every first[t]
+    for t, k in enumerate(nb):
+        assert blk[1][first[t]] == 0 and blk[0][first[t]] == t
+    blk2, nb2 = smo._block_table(numels, "cpu")
+    assert blk2 is blk and nb2 is nb and smo._first_block_table(numels, "cpu") is first
+
+
 def test_train_one_epoch_takes_the_reference_positional_arguments():
     """main.py:825-838 calls ``train_one_epoch(model, criterion, loader, optimizer, device, epoch, loss_scaler, clip_grad,
     model_ema, mixup_fn, set_training_mode=..., args=...)``: positions 9 and 10 are the EMA and the mixup function

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """BASELINE cfg 5 timing: forward + backward (+ AdamW step through NativeScaler) with the SwitchGate, capacity_factor 1.0 and the
 aux loss, (a) for ONE MoE layer at ViT-B dims (T = images x 197 rows) and (b) for the whole ViT-B/16 E=8 model.
-usage: train_bench.py [layer|model] [images] [iters] [model name] [image size]     (run under rocprofv3 --kernel-trace --stats for the per-kernel table)
+usage: train_bench.py [layer|model] [images] [iters] [model name] [image size] [--opt adamw|lamb]     (run under rocprofv3 --kernel-trace --stats for the per-kernel table)
 model name: default moe_base_patch16_224_expert8_top1 with the SwitchGate (cfg 5); a resmoe_* name = the reference's live block
 (token-skip gates, residual on the normed activations, naive gate; thresholds set so that ~40 % of the tokens skip).
 TRAIN_BENCH_EP=static|counted (model mode): the step through the EXPERT-PARALLEL code path on a one-rank RCCL group -- cfg 5's capacity
 gate on the static exchange (fixed slots, counts in-band, no host round trip) or on the counted one (a count read-back per layer).
 TRAIN_BENCH_SOFT_GATES=1 (resmoe_* names): the model is built with soft gates (gate_is_hard=False: skip_tk = 1 - p, tk = p in training).
+--opt lamb (model mode): optim.Lamb (lr 1e-3, weight decay 0.05) in place of optim.AdamW; TRAIN_BENCH_GRAPH=1: the step replayed from
+one HIP graph as well.
 image size: the fifth argument, else the `_<size>_` / `_<size>` field of the model name (moe_large_patch16_384_* -> 384), else 224."""
 import os, re, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +16,12 @@ sys.path.insert(0, ROOT)
 import slim_switch_moe_vit_amd as sm
 from slim_switch_moe_vit_amd import optim as smo
 
+opt_name = "adamw"
+if "--opt" in sys.argv:
+    at = sys.argv.index("--opt")
+    opt_name = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+assert opt_name in ("adamw", "lamb"), opt_name
 what = sys.argv[1] if len(sys.argv) > 1 else "layer"
 images = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 iters = int(sys.argv[3]) if len(sys.argv) > 3 else 10
@@ -98,7 +106,10 @@ else:
         if ep_mode == "static":
             speculative = ep.set_speculative(model, 1.25, train=True) > 0
     model.train()
-    opt = smo.AdamW(model.parameters(), lr=1e-4, weight_decay=0.05)
+    if opt_name == "lamb":
+        opt = smo.Lamb(model.parameters(), lr=1e-3, weight_decay=0.05)
+    else:
+        opt = smo.AdamW(model.parameters(), lr=1e-4, weight_decay=0.05)
     scaler = smo.NativeScaler()
     crit = torch.nn.CrossEntropyLoss()
     x = torch.randn(images, 3, size, size, generator=g).to(dev)
@@ -182,7 +193,7 @@ else:
     extra = ""
     if gates:
         extra = f"; {'soft gates, ' if not gates[0].is_hard else ''}skipped tokens {sum(gt._skipped_tokens for gt in gates) / max(1, sum(gt._total_tokens for gt in gates)):.2f}"
-    print(f"{name} train step (fwd + bwd + clip + AdamW), batch {images}: {t:.2f} ms = {images / t * 1e3:.0f} images/s{extra}", flush=True)
+    print(f"{name} train step (fwd + bwd + clip + {'LAMB' if opt_name == 'lamb' else 'AdamW'}), batch {images}: {t:.2f} ms = {images / t * 1e3:.0f} images/s{extra}", flush=True)
 
     if os.environ.get("TRAIN_BENCH_TRACE"):
         # which host call starts each torch (non-library) kernel of the step: aten op, input shapes, innermost package frames
