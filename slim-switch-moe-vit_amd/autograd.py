@@ -22,18 +22,7 @@ from typing import List
 import torch
 
 from . import ops
-
-
-def switch_aux_loss(idx_pruned: torch.Tensor, probs: torch.Tensor, E: int) -> torch.Tensor:
-    """aux = E * sum_e frac_e * prob_e: frac_e = share of kept tokens routed to e,
-    prob_e = sum_t p[t,e] / kept.  Small [E]-sized reduction; differentiable w.r.t. ``probs``."""
-    flat = idx_pruned.reshape(-1)
-    keep = flat >= 0
-    kept = keep.sum().clamp(min=1).to(probs.dtype)
-    frac = torch.bincount(torch.where(keep, flat, torch.zeros_like(flat)), weights=keep.to(probs.dtype),
-                          minlength=E)[:E] / kept
-    prob = probs.sum(0) / kept
-    return E * (frac * prob).sum()
+from .gates import Routed
 
 
 def _default_cd():
@@ -276,79 +265,6 @@ class _GateLogits(torch.autograd.Function):
         return dx, dw, db, None
 
 
-class _SwitchScoreAux(torch.autograd.Function):
-    """SwitchGate's differentiable outputs from what the HIP router already computed: score = softmax(logits + noise)[idx] and
-    the load-balance loss aux = E sum_e frac_e prob_e (fmoe.gates.SwitchGate).  Forward: the router's probabilities
-    and score, an [E]-sized reduction for aux.  Backward: ONE pass over [T, E] (smoe_switch_gate_bwd) instead of the ~25 small
-    autograd kernels of softmax / gather / bincount / where."""
-
-    @staticmethod
-    def forward(ctx, logits, probs, score, idx, counts, E):
-        # aux and cbase[e] = E frac_e / kept = d aux / d p[t, e] (the same for every t; dropped tokens count nowhere): smoe_switch_aux
-        aux, cbase = ops.switch_aux(probs, counts)
-        ctx.save_for_backward(probs, idx, cbase)
-        ctx.set_materialize_grads(False)     # no aux loss in the objective: daux is None, not a zero tensor
-        return score.view_as(score), aux
-
-    @staticmethod
-    def backward(ctx, dscore, daux):
-        probs, idx, cbase = ctx.saved_tensors
-        if dscore is None and daux is None:
-            return (None,) * 6
-        ds = dscore.reshape(-1).to(torch.float32).contiguous() if dscore is not None else None
-        scale = daux.reshape(1).to(torch.float32) if daux is not None else None      # multiplied onto cbase inside the kernel
-        return (ops.switch_gate_bwd(probs, idx.reshape(-1), ds, cbase if daux is not None else None, scale),
-                None, None, None, None, None)
-
-
-class _GShardScoreAux(torch.autograd.Function):
-    """GShardGate's differentiable outputs from what the HIP router already computed: score = softmax over the two chosen logits and
-    the balance loss aux = mean_e(c_e m_e) num_expert^2 (fmoe.gates.GShardGate).  Forward: the router's score, and
-    smoe_gshard_aux for aux.  Backward: ONE pass over [T, E] (smoe_gshard_gate_bwd); the score gradient of an entry the prune dropped
-    counts as zero."""
-
-    @staticmethod
-    def forward(ctx, logits, score, idx, idx_out, top1, num_expert):
-        aux, coef = ops.gshard_aux(logits, top1, num_expert)
-        ctx.save_for_backward(logits, score, idx, idx_out, coef)
-        ctx.set_materialize_grads(False)     # no aux loss in the objective: daux is None, not a zero tensor
-        return score.view_as(score), aux
-
-    @staticmethod
-    def backward(ctx, dscore, daux):
-        logits, score, idx, idx_out, coef = ctx.saved_tensors
-        if dscore is None and daux is None:
-            return (None,) * 6
-        ds = dscore.to(torch.float32).contiguous() if dscore is not None else None
-        scale = daux.reshape(1).to(torch.float32) if daux is not None else None      # multiplied onto coef inside the kernel
-        return (ops.gshard_gate_bwd(logits, idx, idx_out, score, ds, coef if daux is not None else None, scale),
-                None, None, None, None, None)
-
-
-class _NoisyScoreAux(torch.autograd.Function):
-    """NoisyGate's differentiable outputs from what smoe_noisy_gate_fwd already computed behind the router: score = softmax over the
-    k largest noisy values and aux = cv2(importance) + cv2(load) (fmoe.gates.NoisyGate).  ``logits2`` [T, 2E] =
-    [clean | raw] carries the gradient.  Backward: ONE pass (smoe_noisy_gate_bwd); without the loss in the objective (daux None) its
-    terms are left out."""
-
-    @staticmethod
-    def forward(ctx, logits2, eps, idx, score, keep, nxt, aux, coef_imp, coef_load, training):
-        ctx.training, ctx.has_eps = training, eps is not None
-        ctx.save_for_backward(logits2, idx, keep, nxt, coef_imp, coef_load, *((eps,) if eps is not None else ()))
-        ctx.set_materialize_grads(False)     # no aux loss in the objective: daux is None, not a zero tensor
-        return score.view_as(score), aux.view_as(aux)
-
-    @staticmethod
-    def backward(ctx, dscore, daux):
-        logits2, idx, keep, nxt, coef_imp, coef_load = ctx.saved_tensors[:6]
-        eps = ctx.saved_tensors[6] if ctx.has_eps else None
-        if dscore is None and daux is None:
-            return (None,) * 10
-        ds = dscore.to(torch.float32).contiguous() if dscore is not None else None
-        scale = daux.reshape(1).to(torch.float32) if daux is not None else None      # multiplied onto the coefficients inside the kernel
-        return (ops.noisy_gate_bwd(logits2, eps, idx, keep, nxt, ds, coef_imp, coef_load, scale, ctx.training),) + (None,) * 9
-
-
 def _zero_row_routing(mod):
     """(int64 [k] (device): the experts an all-zero row is routed to (top-k of the gate bias; ties -> lowest id), from the HIP
     router itself; the group -> expert map i32 [E + k]; the zero groups' ids int64 [1, k]), cached per version of the gate parameters."""
@@ -377,54 +293,32 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
     """HIP routing + the differentiable gate score; returns (score, counts, offsets, pos, inv_pos, group map | None, zero groups, S).
     ``scatter_cd``: also scatter the rows (compute dtype) -- S, else None; when the gate's logits carry a gradient the scatter and
     the gate linear are one autograd node (_GateScatter: one gradient for x, no add kernel).
-    ``zero_rows`` (bool [T], NaiveGate only): tokens whose row is all zero (masked by the token-skip gate).  They get row groups of
-    their own -- group E + j for their j-th choice -- that use the expert the gate bias sends every zero row to (the group ->
+    ``zero_rows`` (bool [T]; gates whose zero rows route alike -- ``zero_groups_ok`` -- and without a capacity only): tokens
+    whose row is all zero (masked by the token-skip gate).  They get row groups of their own -- group E + j for their j-th choice -- that use the expert the gate bias sends every zero row to (the group ->
     expert map): same numbers as dispatching them with everybody else, but the experts' own groups stay balanced and the zero
     groups' weight gradients are rank-1 (_GroupFFN.backward).
     ``slots`` (dict with "tab": ep._SlotTable, "agreed": rows the table was agreed for): the plan in the slot layout of the static
     expert exchange (smoe_dispatch_plan_slots: pos has tab.rows entries, S is the send buffer); "counts" / "raw" come back in it."""
-    from .fmoe import GShardGate, NoisyGate, SwitchGate
-
     g = mod.gate
     k = mod.top_k
     T = x.shape[0]
-    is_switch = isinstance(g, SwitchGate)
-    is_gshard = isinstance(g, GShardGate)
-    is_noisy = isinstance(g, NoisyGate)
-    noise = g.make_noise(T, x.device) if is_switch else None
-    score_t = None
-    if is_noisy:
-        # the gate "linear" is the [2E, d] stack [w_gate^T ; w_noise^T], built differentiably from the two parameters: ONE router call
-        # yields clean and raw logits, and its gradients go back through the same nodes as any gate's
-        gate_w, gate_b = g.weight2(), None
-        gw, gb = gate_w.detach(), None
-        eps = g.make_noise(T, x.device) if g.training else None              # (eval: sigma = 0)
-        if not ops.noisy_gate_supported(g.tot_expert, k):                      # outside the kernels' range: the torch composition
-            idx, score_t = g(x.float(), eps)
-    else:
-        gate_w, gate_b = g.gate.weight, g.gate.bias
-        gw = gate_w.detach().float().contiguous()
-        gb = gate_b.detach().float() if gate_b is not None else None
-    need_grad = is_switch or k > 1 or is_noisy
+    E = g.tot_expert
+    r = Routed()
+    gate_w, gate_b, router_k, noise, r.state = g.train_begin(T, x.device)
+    torch_route = g.train_torch(x, r.state)      # outside the kernels' range: the torch composition
+    need_grad = g.score_grad
     g_map, zero_groups = None, 0
     with torch.no_grad():
-        if score_t is not None:
-            score_c, logits_r = score_t.detach().float().contiguous(), None
-        elif is_noisy:
-            # (the router's own top-1 over the 2E columns is discarded: the decision is taken on the f32 noisy values)
-            _, _, logits_r, probs_r = ops.router_topk(x.detach(), gw, None, 1, ops.GATE_NAIVE, None, want_logits=True)
-            nz = ops.noisy_gate_fwd(logits_r, eps, k, g.training)
-            idx, score_c = nz["idx"], nz["score"]
-            g.last_noise = (eps, nz["imp"], nz["load"])
+        if torch_route is not None:
+            r.idx, r.score, r.logits = torch_route[0], torch_route[1].detach().float().contiguous(), None
+            plan = g.plan_input(r.idx, r.score, T)
         else:
-            idx, score_c, logits_r, probs_r = ops.router_topk(x.detach(), gw, gb, k, g.kind, noise, want_logits=need_grad,
-                                                              want_probs=is_switch)
-        cap = g.capacity(T)
-        E = g.tot_expert
-        plan_idx, plan_cap = idx, cap
-        if is_gshard:   # capacity + random routing on the gate's own kernels; the plan over what is left has no capacity of its own
-            (idx_out, top1), plan_cap = g.prune(idx, score_c), -1
-            plan_idx = idx_out
+            gw = gate_w.detach().float().contiguous()
+            gb = gate_b.detach().float() if gate_b is not None else None
+            r.idx, r.score, r.logits, r.probs = ops.router_topk(x.detach(), gw, gb, router_k, g.kind, noise, want_logits=need_grad,
+                                                                want_probs=g.want_probs)
+            plan = g.train_step(r, T)
+        plan_idx, plan_cap = r.plan_idx, r.plan_cap = plan
         if slots is not None:
             tab, agreed = slots["tab"], slots["agreed"]
             if T <= agreed:
@@ -435,40 +329,27 @@ def _route_train(mod, x, zero_rows=None, scatter_cd=None, slots=None):
                 inv_pos = torch.full((T * k,), -1, dtype=torch.int64, device=x.device)
                 inv_pos[: agreed * k].copy_(inv_h)
             slots["counts"], slots["raw"] = counts, raw
-        elif zero_rows is not None and not is_switch and not is_gshard and not is_noisy and cap < 0 and E + k <= 63:
-            # (nor for a NoisyGate: with noise, masked rows do not route alike)
-            # (not for a GShardGate without a capacity: its plan runs over the pruned ids -- random routing still drops entries)
+        elif zero_rows is not None and g.zero_groups_ok and plan_cap < 0 and E + k <= 63:
             _idx0, g_map, zero_ids = _zero_row_routing(mod)                                # (cached per gate-parameter version)
-            idx_plan = torch.where(zero_rows.reshape(T, 1), zero_ids, idx)
-            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx_plan, E + k, cap)
+            idx_plan = torch.where(zero_rows.reshape(T, 1), zero_ids, r.idx)
+            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx_plan, E + k, plan_cap)
             zero_groups = k
         else:
             counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(plan_idx, E, plan_cap)
-    mod.last_plan = (idx, score_c, counts, offsets, pos, inv_pos)
+    mod.last_plan = (r.idx, r.score, counts, offsets, pos, inv_pos)
     S = None
-    if score_t is not None:
-        score = score_t.float()
+    if torch_route is not None:
+        score = torch_route[1].float()
     elif need_grad:  # tiny [T,E] work -- the routing itself stays the HIP router's
         fused = (scatter_cd is not None and x.is_cuda and x.shape[1] % 4 == 0 and x.dtype in ops._DT
                  and gate_w.dtype == torch.float32)
         if fused:
-            logits, S = _GateScatter.apply(x, gate_w, gate_b, logits_r, pos, inv_pos, k, scatter_cd)
+            logits, S = _GateScatter.apply(x, gate_w, gate_b, r.logits, pos, inv_pos, k, scatter_cd)
         else:
-            logits = _GateLogits.apply(x, gate_w, gate_b, logits_r)
-        if is_noisy:    # score and loss are smoe_noisy_gate_fwd's own; one node carries both back to the [T, 2E] logits
-            score, aux = _NoisyScoreAux.apply(logits, eps, idx, score_c, nz["keep"], nz["next"], nz["aux"], nz["coef_imp"],
-                                              nz["coef_load"], g.training)
-            g.set_loss(aux)
-        elif is_switch:   # probs_r = softmax(logits + noise) and score_c = probs_r[idx] are the router's own
-            score, aux = _SwitchScoreAux.apply(logits, probs_r, score_c, idx, counts, g.tot_expert)
-            g.set_loss(aux)
-        elif is_gshard:  # score_c = softmax over the two chosen logits is the router's own; aux from the logits and the first choices
-            score, aux = _GShardScoreAux.apply(logits, score_c, idx, idx_out, top1, g.num_expert)
-            g.set_loss(aux)
-        else:
-            score = torch.softmax(logits.gather(1, idx), dim=-1)
+            logits = _GateLogits.apply(x, gate_w, gate_b, r.logits)
+        score = g.train_score(logits, r, counts)     # (and the gate's loss: one node carries both back to the logits)
     else:
-        score = score_c  # top-1 naive gate: softmax over one logit == 1, no gradient (SURVEY.md 'DDP + top-1')
+        score = r.score  # top-1 naive gate: softmax over one logit == 1, no gradient (SURVEY.md 'DDP + top-1')
     if S is None and scatter_cd is not None:
         S = _Scatter.apply(x, pos, inv_pos, k, scatter_cd)
     return score, counts, offsets, pos, inv_pos, g_map, zero_groups, S

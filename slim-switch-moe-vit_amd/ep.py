@@ -30,6 +30,7 @@ import torch
 import torch.distributed as dist
 
 from ._cache import StreamCache
+from .gates import Routed, route_nograd
 
 
 class _DoneWork:
@@ -654,7 +655,7 @@ def exchange_counts_static(counts: torch.Tensor, T: int, W: int, group=None):
     return both[1, :, :E_local].reshape(-1), both[1, :, E_local]
 
 
-def _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, next_norm, agreed: int, kind: str):
+def _ep_forward_static(mod, x, r, cd, residual, next_norm, agreed: int, kind: str):
     """Expert-parallel forward on STATIC buffers ("cfg 5 (capacity-bounded) can use fixed-size padded
     buffers -> no host sync"; Appendix B's `cap` note) -- for a capacity gate (``kind`` "capacity": a rank keeps at most `cap` of
     its rows per global expert) and, speculatively, for a gate without one ("speculative": slots of alpha x the balanced share,
@@ -669,7 +670,6 @@ def _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, n
     than its slot, keeps the agreed buffer shape (it drops what does not fit; its peers must not hang) and the violation is raised
     on every rank by check_static_overflow -- never here, by this rank alone."""
     from . import ops
-    from .fmoe import GShardGate, SwitchGate
 
     g = mod.gate
     W, E_local, k, d = mod.world_size, mod.num_expert, mod.top_k, mod.d_model
@@ -679,11 +679,11 @@ def _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, n
     dev = x.device
     st = _slot_state(mod, kind, agreed, dev)
     tab = st.table
-    counts = raw = None
+    idx, score, plan_idx = r.idx, r.score, r.plan_idx
+    counts = raw = pruned = None
     if T > 0:
-        cap = g.capacity(T) if kind == "capacity" else -1               # (on top of the slots: what THIS batch may keep)
-        if isinstance(g, GShardGate):
-            cap = -1                                                    # (plan_idx is the gate's own pruned ids: already within it)
+        # (on top of the slots: what THIS batch may keep; -1 where plan_idx is the gate's own pruned ids, already within it)
+        cap = r.plan_cap if kind == "capacity" else -1
         if T <= agreed:
             counts, offsets, gend, pos, inv_pos, pruned, raw = ops.dispatch_plan_slots(plan_idx, E_tot, tab.base_dev, tab.rows, cap)
         else:
@@ -694,16 +694,14 @@ def _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, n
             inv_pos[: agreed * k].copy_(inv_h)
             pruned = torch.full((T * k,), -1, dtype=torch.int64, device=dev)
             pruned[: agreed * k].copy_(pruned_h)
-        send = ops.scatter_rows(src, pos, k, cd)                        # [tab.rows, d]; unused slots stay unwritten
+        send = ops.scatter_rows(r.src, pos, k, cd)                      # [tab.rows, d]; unused slots stay unwritten
         mod.last_plan = (idx, score, counts, offsets, pos, inv_pos)
-        if isinstance(g, SwitchGate):
-            from .autograd import switch_aux_loss
-            g.set_loss(switch_aux_loss(pruned, probs, E_tot))
     else:
         inv_pos = torch.empty((0,), dtype=torch.int64, device=dev)
         send = torch.empty((tab.rows, d), dtype=cd, device=dev)
         mod.last_plan = (idx, score, torch.zeros(E_tot, dtype=torch.int32, device=dev),
                          torch.zeros(E_tot + 1, dtype=torch.int32, device=dev), None, inv_pos)
+    g.nograd_loss(pruned, r.probs)      # (a rank without rows planned nothing: pruned is None)
     # the counts, this rank's row count and its whole routing histogram ride in the header rows; nobody on the host reads them
     ops.ep_pack_headers(send, counts, raw, tab.base_dev, T)
     recv = torch.empty((tab.recv_rows, d), dtype=cd, device=dev)
@@ -768,7 +766,6 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
     ONE pass) the routing is taken as given: ``idx`` / ``score`` [T, k], ``idx_plan`` (= idx, -1 for the tokens the skip gate
     masked: they are simply not sent), ``src`` = the 16-bit operand image the send buffers are gathered from."""
     from . import ops
-    from .fmoe import GShardGate, NoisyGate, SwitchGate
 
     g = mod.gate
     W, E_local, k, d = mod.world_size, mod.num_expert, mod.top_k, mod.d_model
@@ -776,65 +773,40 @@ def ep_forward_steps(mod, x: torch.Tensor, cd: torch.dtype, residual: Optional[t
     T = x.shape[0]
     cap = g.capacity(T)
     check_static_overflow()      # (deferred, deterministic: every rank reads the same row-count vectors at the same call)
-    # capacity is defined over the whole local batch, so dropping gates run un-chunked
+    # capacity is defined over the whole local batch, so dropping gates run un-chunked (`cap` is the gate's own figure: it keeps
+    # deciding this for a gate whose plans run over its own pruned ids, without a capacity)
     n_chunks = 1 if cap >= 0 else max(1, int(getattr(mod, "ep_chunks", 1)))
     bounds = chunk_bounds(T, n_chunks) if T > 0 else [(0, 0)] * n_chunks
     if len(bounds) < n_chunks:  # tiny batches: keep the collective count identical on every rank
         bounds = bounds + [(T, T)] * (n_chunks - len(bounds))
 
-    noise = g.make_noise(T, x.device) if isinstance(g, SwitchGate) else None
-    gw = g.gate.weight.detach().float().contiguous()
-    gb = g.gate.bias.detach().float() if g.gate.bias is not None else None
-    src = x  # rows the send buffers are gathered from
-    plan_idx = None
     if routed is not None:
-        idx, score, probs, src = routed["idx"], routed["score"], None, routed["src"]
-        plan_idx = routed.get("idx_plan")
-    elif T == 0:   # a rank without rows still takes part in every collective of the layer
-        idx = torch.empty((0, k), dtype=torch.int64, device=x.device)
-        score = torch.empty((0, k), dtype=torch.float32, device=x.device)
-        probs = torch.empty((0, g.tot_expert), dtype=torch.float32, device=x.device)
-        src = torch.empty((0, d), dtype=cd, device=x.device) if norm is not None else x
-    elif isinstance(g, NoisyGate) and g.training:
-        # a no-grad forward of a module left in training mode routes with noise (the fused LayerNorm pass is not offered to it)
-        assert norm is None, "ep_forward_steps: a NoisyGate in training mode takes the unfused sequence"
-        (idx, score), probs = g.route_noisy(x), None
-    elif norm is not None:
-        xn16, _, idx, score, _, probs = ops.ln_router_topk(
-            x, norm.weight.detach().float(), norm.bias.detach().float() if norm.bias is not None else None, norm.eps,
-            gw, gb, k, g.kind, noise, xn16_dtype=cd, want_probs=isinstance(g, SwitchGate))
-        src = xn16
-    else:
-        idx, score, _, probs = ops.router_topk(x, gw, gb, k, g.kind, noise, want_probs=isinstance(g, SwitchGate))
-    if plan_idx is None:
-        plan_idx = idx
-    if isinstance(g, NoisyGate):
-        g.set_loss(None)
-    if isinstance(g, GShardGate):
-        # capacity (per source rank, on this rank's T rows) + random routing on the gate's own kernels: every plan below runs over
-        # what is left, without a capacity of its own.  `cap` keeps deciding what a capacity gate decides (one chunk, static exchange).
-        if routed is not None:    # (a caller's idx_plan -- the skip gate's -1 entries -- would be lost under the prune below)
+        if g.prunes:    # (a caller's idx_plan -- the skip gate's -1 entries -- would be lost under the gate's own prune)
             raise NotImplementedError("ep_forward_steps: a GShardGate takes no pre-routed batch (norm_gate_fusable is the NaiveGate's)")
-        g.set_loss(None)
-        if T > 0:
-            plan_idx = g.prune(idx, score)[0]
-        plan_cap = -1
+        r = Routed()
+        r.idx, r.score, r.probs, r.src = routed["idx"], routed["score"], None, routed["src"]    # src: the rows the sends gather from
+        r.plan_idx, r.plan_cap = routed["idx_plan"] if routed.get("idx_plan") is not None else r.idx, cap
+    elif T == 0:   # a rank without rows still takes part in every collective of the layer
+        r = Routed()
+        r.idx = torch.empty((0, k), dtype=torch.int64, device=x.device)
+        r.score = torch.empty((0, k), dtype=torch.float32, device=x.device)
+        r.probs = torch.empty((0, g.tot_expert), dtype=torch.float32, device=x.device)
+        r.src = torch.empty((0, d), dtype=cd, device=x.device) if norm is not None else x
+        r.plan_idx, r.plan_cap = g.plan_input(r.idx, r.score, 0)
     else:
-        plan_cap = cap
+        r = route_nograd(mod, x, norm, cd, want_hist=False)      # (the plans below run per chunk)
+    idx, score, src = r.idx, r.score, r.src
     kind = static_kind(mod, cd)
     if kind is not None:
         # decided from the configuration and the AGREED row count only: every rank takes the same branch whatever its batch
         agreed = static_slot_tokens(mod, T, x.device)
         if static_plan_fits(mod, agreed):
-            return (yield from _ep_forward_static(mod, x, src, idx, plan_idx, score, probs, cd, residual, next_norm, agreed, kind))
+            return (yield from _ep_forward_static(mod, x, r, cd, residual, next_norm, agreed, kind))
     plans = []
     for (t0, t1) in bounds:
-        plans.append(ops.dispatch_plan(plan_idx[t0:t1], g.tot_expert, plan_cap))
+        plans.append(ops.dispatch_plan(r.plan_idx[t0:t1], g.tot_expert, r.plan_cap))
     mod.last_plan = (idx, score) + tuple(plans[0][:4])
-    if isinstance(g, SwitchGate):
-        from .autograd import switch_aux_loss
-        pruned = plans[0][4] if plans[0][4] is not None else idx
-        g.set_loss(switch_aux_loss(pruned, probs, g.tot_expert))
+    g.nograd_loss(plans[0][4] if plans[0][4] is not None else idx, r.probs)
 
     pending = exchange_counts_start([p[0] for p in plans], W, group)
     # Nothing below depends on the HOST knowing the counts: the send buffers' scatter, the received groups' row offsets (built on

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import ops
 from ._cache import StreamCache, param_version, register_shadow
+from .gates import GShardGate, NaiveGate, NoisyGate, SwitchGate, route_nograd  # noqa: F401  (re-exported: the gates' home is gates.py)
 
 _COMPUTE_DTYPES = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
 
@@ -90,223 +91,6 @@ class FMoELinear(nn.Module):
 
     def extra_repr(self):
         return f"num_expert={self.num_expert}, in_features={self.in_feat}, out_features={self.out_feat}"
-
-
-class NaiveGate(nn.Module):
-    """``gate = nn.Linear(d_model, num_expert * world_size)``; top-k of the logits, softmax over the kept k."""
-
-    kind = ops.GATE_NAIVE
-
-    def __init__(self, d_model: int, num_expert: int, world_size: int, top_k: int = 2):
-        super().__init__()
-        self.gate = nn.Linear(d_model, num_expert * world_size)
-        self.top_k = top_k
-        self.num_expert, self.world_size = num_expert, world_size
-        self.tot_expert = num_expert * world_size
-        self.loss = None
-
-    def capacity(self, n_tokens: int) -> int:
-        return -1
-
-    def set_loss(self, loss):
-        self.loss = loss
-
-    def get_loss(self, clear: bool = True):
-        loss = self.loss
-        if clear:
-            self.loss = None
-        return loss
-
-
-class SwitchGate(NaiveGate):
-    """Switch-Transformer top-1 gate with capacity and load-balance loss (fmoe.gates.SwitchGate).
-
-    ``capacity_factor`` follows the Switch definition per source rank: cap = ceil(cf * T_local * k / E_total);
-    ``capacity_mode="fmoe"`` selects upstream's ceil(cf * T_local) instead (cf = (train, eval) pair)."""
-
-    kind = ops.GATE_SWITCH
-
-    def __init__(self, d_model: int, num_expert: int, world_size: int, top_k: int = 1, switch_eps: float = 0.1,
-                 capacity=(1.2, 2.4), capacity_mode: str = "switch"):
-        assert top_k == 1, "SwitchGate is top-1"
-        super().__init__(d_model, num_expert, world_size, top_k=1)
-        self.switch_eps = switch_eps
-        self.capacity_factor = capacity
-        self.capacity_mode = capacity_mode
-
-    def capacity(self, n_tokens: int) -> int:
-        cf = self.capacity_factor
-        if cf is None:
-            return -1
-        if isinstance(cf, (tuple, list)):
-            cf = cf[0] if self.training else cf[1]
-        if self.capacity_mode == "fmoe":
-            return int(math.ceil(cf * n_tokens))
-        return int(math.ceil(cf * n_tokens * self.top_k / self.tot_expert))
-
-    def make_noise(self, T: int, device) -> Optional[torch.Tensor]:
-        if not self.training or self.switch_eps <= 0:
-            return None
-        # upstream adds U[0,1) * 2*eps + (1 - eps) to the logits: one generator kernel (uniform_ applies the affine map itself)
-        return torch.empty(T, self.tot_expert, device=device).uniform_(1.0 - self.switch_eps, 1.0 + self.switch_eps)
-
-
-class GShardGate(NaiveGate):
-    """GShard top-2 gate with a per-expert capacity, the GShard balance loss and random routing of the second choice
-    (fmoe.gates.GShardGate; the rule is restated in INTEGRATION.md).  The routing is the naive top-2 router's; this gate's own
-    arithmetic runs behind it on smoe_gshard_prune / _aux / _gate_bwd.
-
-    ``capacity`` = (train, eval) rates or one rate for both: cap = (ceil(rate * T_local) * 2) // E_total entries per expert, applied
-    per source rank in flat order (entry 2 t + j).  ``random_routing``: the second choice of token t is dropped when
-    2 * score[t, 1] < u[t], u ~ U[0, 1) -- in training AND in eval, as upstream; pass False for a deterministic gate."""
-
-    kind = ops.GATE_NAIVE
-
-    def __init__(self, d_model: int, num_expert: int, world_size: int, topk: int = 2, capacity=(1.2, 2.4),
-                 random_routing: bool = True, gate_bias: bool = True):
-        assert topk == 2, "GShardGate is top-2"
-        super().__init__(d_model, num_expert, world_size, top_k=2)
-        if not gate_bias:
-            self.gate = nn.Linear(d_model, self.tot_expert, bias=False)
-        self.capacity_factor = capacity
-        self.random_routing = random_routing
-        self.last_routing = None  # (u | None, idx_out, top1_counts) of the latest forward, for inspection
-
-    def capacity(self, n_tokens: int) -> int:
-        cf = self.capacity_factor
-        if cf is None:
-            return -1
-        if isinstance(cf, (tuple, list)):
-            cf = cf[0] if self.training else cf[1]
-        return (int(math.ceil(cf * n_tokens)) * self.top_k) // self.tot_expert
-
-    def make_uniform(self, T: int, device) -> Optional[torch.Tensor]:
-        return torch.rand(T, device=device) if self.random_routing else None
-
-    def prune(self, idx: torch.Tensor, score: torch.Tensor):
-        """(idx_out, top1_counts) for the router's ``idx`` / ``score`` [T, 2]: capacity, then random routing (ops.gshard_prune).  The
-        dispatch plan then runs over ``idx_out`` without a capacity of its own."""
-        T = idx.shape[0]
-        u = self.make_uniform(T, idx.device)
-        idx_out, top1 = ops.gshard_prune(idx, score, u, self.tot_expert, self.capacity(T))
-        self.last_routing = (u, idx_out, top1)
-        return idx_out, top1
-
-
-class _GateImage:
-    """What the naive paths read as ``gate.gate`` of a NoisyGate: ``weight`` = the [E, d] f32 image of ``w_gate`` (no gradient), no bias."""
-    __slots__ = ("weight", "bias")
-
-    def __init__(self, weight):
-        self.weight, self.bias = weight, None
-
-
-class NoisyGate(nn.Module):
-    """Noisy top-k gate with the importance + load balance loss and no capacity (fmoe.gates.NoisyGate, Shazeer et al.; the rule is
-    restated in INTEGRATION.md).  Parameters ``w_gate`` / ``w_noise`` [d_model, E], no bias.  In training the router runs over the
-    [2E, d] image [w_gate^T ; w_noise^T] and the gate's own arithmetic runs behind it on smoe_noisy_gate_fwd / _bwd; in eval
-    (sigma = 0) the gate IS a bias-free NaiveGate over ``w_gate.T``: ``gate.gate`` hands every naive path that [E, d] image (cached
-    per parameter version; not a sub-module, so the state dict holds ``w_gate`` and ``w_noise`` and nothing else).
-    Calling the module (``gate(x)`` -> (idx, score)) is the differentiable torch composition of the rule: CPU tensors, and the
-    configurations the kernels do not take."""
-
-    kind = ops.GATE_NAIVE
-
-    def __init__(self, d_model: int, num_expert: int, world_size: int, top_k: int = 2):
-        super().__init__()
-        self.top_k = top_k
-        self.num_expert, self.world_size = num_expert, world_size
-        self.tot_expert = num_expert * world_size
-        if not 1 <= top_k < self.tot_expert:
-            # (upstream falls back to a count-based, non-differentiable load at top_k >= E: refused instead)
-            raise ValueError(f"NoisyGate: top_k={top_k} must be in [1, E) for E={self.tot_expert} experts (the load reads the "
-                             f"(k+1)-th value)")
-        self.w_gate = nn.Parameter(torch.empty(d_model, self.tot_expert))
-        self.w_noise = nn.Parameter(torch.empty(d_model, self.tot_expert))
-        self.noise_epsilon = 1e-2
-        self.loss = None
-        self.last_noise = None   # (eps, imp, load) of the latest training forward, for inspection
-        self._images = StreamCache()
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod._images.invalidate())
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        nn.init.kaiming_uniform_(self.w_gate, a=math.sqrt(5))
-        nn.init.kaiming_uniform_(self.w_noise, a=math.sqrt(5))
-
-    def capacity(self, n_tokens: int) -> int:
-        return -1
-
-    def set_loss(self, loss):
-        self.loss = loss
-
-    def get_loss(self, clear: bool = True):
-        loss = self.loss
-        if clear:
-            self.loss = None
-        return loss
-
-    def make_noise(self, T: int, device) -> torch.Tensor:
-        return torch.randn(T, self.tot_expert, device=device)
-
-    @property
-    def gate(self) -> _GateImage:
-        w = self.w_gate
-        return _GateImage(self._images.get(("t", w.device), param_version(w), lambda: w.detach().t().float().contiguous()))
-
-    def weight2(self) -> torch.Tensor:
-        """[2E, d] = [w_gate^T ; w_noise^T], differentiable: the operand of the one router call that yields clean and raw logits."""
-        return torch.cat((self.w_gate.t(), self.w_noise.t()), 0).float()
-
-    def image2(self) -> torch.Tensor:
-        """``weight2()`` without a gradient, cached per version of the two parameters."""
-        ver = (param_version(self.w_gate), param_version(self.w_noise))
-        return self._images.get(("2", self.w_gate.device), ver, lambda: self.weight2().detach().contiguous())
-
-    def route_noisy(self, x: torch.Tensor):
-        """(idx, score) of a no-grad forward of a gate left in training mode: router over the [2E, d] image (its own top-1 is
-        discarded), then smoe_noisy_gate_fwd with a fresh draw.  No loss."""
-        T, E, k = x.shape[0], self.tot_expert, self.top_k
-        self.set_loss(None)
-        with torch.no_grad():
-            if not ops.noisy_gate_supported(E, k):
-                return self.forward(x.float())
-            _, _, logits2, _ = ops.router_topk(x, self.image2(), None, 1, ops.GATE_NAIVE, None, want_logits=True)
-            eps = self.make_noise(T, x.device)
-            r = ops.noisy_gate_fwd(logits2, eps, k, True)
-            self.last_noise = (eps, r["imp"], r["load"])
-        return r["idx"], r["score"]
-
-    @staticmethod
-    def cv2(v: torch.Tensor) -> torch.Tensor:
-        return v.var(unbiased=True) / (v.mean() ** 2 + 1e-10)
-
-    def forward(self, inp: torch.Tensor, eps: Optional[torch.Tensor] = None):
-        """(idx int64 [T, k], score [T, k]) by the rule as differentiable torch ops; sets the loss (None without grad)."""
-        E, k = self.tot_expert, self.top_k
-        x = inp.reshape(-1, inp.shape[-1])
-        clean = x @ self.w_gate.to(x.dtype)
-        if self.training:
-            sigma = torch.nn.functional.softplus(x @ self.w_noise.to(x.dtype)) + self.noise_epsilon
-            if eps is None:
-                eps = self.make_noise(x.shape[0], x.device)
-            noisy = clean + eps.to(x.dtype) * sigma
-        else:
-            noisy = clean
-        val, order = torch.sort(noisy, dim=1, descending=True, stable=True)      # (stable: ties -> lowest expert id)
-        idx, v = order[:, :k], val[:, :k + 1]
-        score = torch.softmax(v[:, :k], dim=-1)
-        if not (torch.is_grad_enabled() and (x.requires_grad or self.w_gate.requires_grad or self.w_noise.requires_grad)):
-            self.set_loss(None)
-            return idx, score
-        imp = torch.zeros(E, dtype=score.dtype, device=x.device).scatter_add(0, idx.reshape(-1), score.reshape(-1))
-        aux = self.cv2(imp)
-        if self.training:
-            thr = torch.where(noisy > v[:, k:k + 1], v[:, k:k + 1], v[:, k - 1:k])
-            load = (0.5 * (1.0 + torch.erf((clean - thr) / sigma * (1.0 / math.sqrt(2.0))))).sum(0)
-            aux = aux + self.cv2(load)
-        self.set_loss(aux)
-        return idx, score
 
 
 class _Expert(nn.Module):
@@ -383,7 +167,7 @@ class FMoETransformerMLP(nn.Module):
 
     forward(x[..., d]) -> same shape:  router -> dispatch plan -> token scatter -> grouped GEMM (+bias,
     +GELU) -> grouped GEMM (+bias) -> gather/combine, all HIP kernels.
-    Keyword-only extensions with reference defaults: ``gate`` ("naive" | "switch" | "gshard" | "noisy" | a gate class),
+    Keyword-only extensions with reference defaults: ``gate`` ("naive" | "switch" | "gshard" | "noisy" | a gate class of gates.py's surface),
     ``capacity_factor``, ``world_size`` / ``moe_group`` (expert parallel), ``compute_dtype``.
     """
 
@@ -489,7 +273,7 @@ class FMoETransformerMLP(nn.Module):
               and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())
                                                     or any(p.requires_grad for p in norm.parameters())))
               and ops.ln_router_supported(self.d_model, g.tot_expert, g.top_k)
-              and not (isinstance(g, NoisyGate) and g.training))    # (noise: the unfused sequence, _route / ep_forward_steps)
+              and g.fused_pass_ok())    # (a noisy gate in training mode: the unfused sequence, _route / ep_forward_steps)
         if not ok:
             return self.forward_add(norm(x), x)
         if self.ep_active():
@@ -507,33 +291,11 @@ class FMoETransformerMLP(nn.Module):
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         T = x2.shape[0]
-        is_switch = isinstance(g, SwitchGate)
-        noise = g.make_noise(T, x2.device) if is_switch else None
-        gw = g.gate.weight.detach().float().contiguous()
-        gb = g.gate.bias.detach().float() if g.gate.bias is not None else None
         cap = g.capacity(T)
         sub = None                # (period, prefix): the rows the experts run for, when the caller reads no others
         if tail is not None and cap < 0 and tail[0] > 0 and T % tail[0] == 0 and 0 < tail[1] < tail[0]:
             sub = (int(tail[0]), int(tail[1]))
-        # the router pass also counts for the plan (count_by_gate folded in) -- over all rows: of no use to a plan over some
-        # (not for a GShardGate: its plan runs over the pruned ids, which the router has not seen)
-        is_gshard = isinstance(g, GShardGate)
-        if isinstance(g, NoisyGate):
-            g.set_loss(None)      # (eval: sigma = 0, the gate is the bias-free NaiveGate over w_gate.T from here on)
-        hist = ops.chunk_hist(T, d, g.tot_expert, k, x2.device) if sub is None and not is_gshard else None
-        xn16, _, idx, score, _, probs = ops.ln_router_topk(
-            x2, norm.weight.detach().float(), norm.bias.detach().float() if norm.bias is not None else None, norm.eps,
-            gw, gb, k, g.kind, noise, xn16_dtype=cd, want_probs=is_switch, hist=hist)
-        if is_gshard:     # capacity + random routing on the gate's own kernels; the plan over what is left has no capacity of its own
-            g.set_loss(None)
-            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(g.prune(idx, score)[0], g.tot_expert, -1, want_pruned=False,
-                                                                      subset=sub)
-        else:
-            counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap, hist=hist, subset=sub)
-        self.last_plan = (idx, score, counts, offsets, pos, inv_pos)
-        if is_switch:
-            from .autograd import switch_aux_loss
-            g.set_loss(switch_aux_loss(pruned if pruned is not None else idx, probs, g.tot_expert))
+        xn16, score, offsets, pos, inv_pos = self._route(x2, norm, cd, sub)
         w1, b1, w2, b2 = operands = self.expert_operands(cd)
         if next_norm is not None and TAIL_MODE == "ln" and _tail_ln_ok(next_norm, x2, cd, k):
             # GEMM-2 stores plain 16-bit rows straight from its accumulators (the direct-store epilogue: no row map, no f32 residual
@@ -603,7 +365,7 @@ class FMoETransformerMLP(nn.Module):
         return (x.is_cuda and x.dtype == torch.float32 and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine
                 and tuple(norm.normalized_shape) == (self.d_model,) and self._fused_gelu and not self.training
                 and cd in (torch.float16, torch.bfloat16) and self.gemm_variant in (4, 9) and self.d_model % 64 == 0
-                and not torch.is_grad_enabled() and type(g) is NaiveGate
+                and not torch.is_grad_enabled() and g.skip_gate_fusable()
                 and ops.gate_ln_router_supported(self.d_model, g.tot_expert, g.top_k))
 
     def zero_row_output(self) -> torch.Tensor:
@@ -667,11 +429,11 @@ class FMoETransformerMLP(nn.Module):
             if self.ep_active():
                 yield from ep_forward_steps(self, x2, cd, residual=x2, routed=empty)
             return x2.reshape(shape)
+        wg, bg = g.router_operands()
         r = ops.gate_ln_router(
             x2, lin.weight, lin.bias, thr,
             ln=(norm.weight.detach(), norm.bias.detach() if norm.bias is not None else None, norm.eps),
-            wg=g.gate.weight.detach().float().contiguous(), bg=g.gate.bias.detach().float() if g.gate.bias is not None else None,
-            k=k, xn16_dtype=cd, want_xn32=True, zero_out=zero_out,
+            wg=wg, bg=bg, k=k, xn16_dtype=cd, want_xn32=True, zero_out=zero_out,
             skip_count=skip_gate.skip_counter(x.device) if thr is not None else None,
             hist=(hist := ops.chunk_hist(T, d, g.tot_expert, k, x2.device)))
         idx, score, out = r["idx"], r["score"], r["xn32"]
@@ -694,30 +456,15 @@ class FMoETransformerMLP(nn.Module):
             return moe_forward_train(self, inp)
         return self._forward_infer(inp)
 
-    def _route(self, x: torch.Tensor):
+    def _route(self, x: torch.Tensor, norm=None, cd=None, sub=None):
+        """The single-rank no-grad routing: gates.route_nograd (with ``norm``: fused with that LayerNorm), the dispatch plan (over
+        the row subset ``sub``), ``last_plan`` and the gate's loss.  Returns (src, score, offsets, pos, inv_pos)."""
         g = self.gate
-        T = x.shape[0]
-        if isinstance(g, NoisyGate):
-            g.set_loss(None)
-            if g.training:        # a no-grad forward of a module left in training mode routes with noise
-                idx, score = g.route_noisy(x)
-                counts, offsets, pos, inv_pos, _ = ops.dispatch_plan(idx, g.tot_expert, -1)
-                return idx, score, None, counts, offsets, pos, inv_pos, None
-        noise = g.make_noise(T, x.device) if isinstance(g, SwitchGate) else None
-        want_probs = isinstance(g, SwitchGate)
-        gw = g.gate.weight.detach()
-        gb = g.gate.bias.detach() if g.gate.bias is not None else None
-        if gw.dtype != torch.float32:
-            gw, gb = gw.float(), (gb.float() if gb is not None else None)
-        idx, score, _, probs = ops.router_topk(x, gw.contiguous(), gb, g.top_k, g.kind, noise, want_probs=want_probs)
-        if isinstance(g, GShardGate):   # capacity + random routing on the gate's own kernels, then a plan without a capacity
-            g.set_loss(None)            # (no balance loss in a no-grad forward: nothing reads it, and it would cost a logits store)
-            idx_out, _ = g.prune(idx, score)
-            counts, offsets, pos, inv_pos, _ = ops.dispatch_plan(idx_out, g.tot_expert, -1)
-            return idx, score, probs, counts, offsets, pos, inv_pos, idx_out
-        cap = g.capacity(T)
-        counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(idx, g.tot_expert, cap)
-        return idx, score, probs, counts, offsets, pos, inv_pos, pruned
+        r = route_nograd(self, x, norm, cd, sub)
+        counts, offsets, pos, inv_pos, pruned = ops.dispatch_plan(r.plan_idx, g.tot_expert, r.plan_cap, hist=r.hist, subset=sub)
+        self.last_plan = (r.idx, r.score, counts, offsets, pos, inv_pos)
+        g.nograd_loss(pruned if pruned is not None else r.idx, r.probs)
+        return r.src, r.score, offsets, pos, inv_pos
 
     def _experts_fwd(self, rows: torch.Tensor, offsets: torch.Tensor, cd: torch.dtype, out=None, row_map=None,
                      row_scale=None, out_dtype=None, group_expert=None, residual=None, group_end=None, rows_hint=None):
@@ -753,11 +500,7 @@ class FMoETransformerMLP(nn.Module):
         if self.world_size > 1 or getattr(self, "force_ep", False):
             from .ep import ep_forward
             return ep_forward(self, x, cd, residual=res).reshape(shape)
-        idx, score, probs, counts, offsets, pos, inv_pos, pruned = self._route(x)
-        self.last_plan = (idx, score, counts, offsets, pos, inv_pos)
-        if isinstance(self.gate, SwitchGate):
-            from .autograd import switch_aux_loss
-            self.gate.set_loss(switch_aux_loss(pruned if pruned is not None else idx, probs, self.gate.tot_expert))
+        _, score, offsets, pos, inv_pos = self._route(x)
         buf = ops.scatter_rows(x, pos, k, cd)
         if k == 1:
             # fused combine: GEMM-2 stores row s to out[pos[s]] * score[pos[s]]; dropped tokens stay 0

@@ -530,3 +530,109 @@ def test_gate_kernel_writes_the_masked_f32_image_in_the_same_pass(d, with_ln):
     assert torch.equal(r["tk32"], r["xn32"] * r["mask"][:, 1:])
     both = ops.gate_ln_router(x, w, b, thr, ln=ln, xn16_dtype=torch.float16, want_xn32=True, want_mask=True, want_tk32=True)
     assert torch.equal(both["tk32"], r["tk32"]) and torch.equal(both["xn16"], r["tk32"].half())
+
+
+# ------------------------------------------------------------------------------- the loss state a routing gate is left in, per site
+_LOSS_GATES = {"naive": ("naive", 1), "switch": ("switch", 1), "gshard": ("gshard", 2), "noisy": ("noisy", 2)}
+# gate -> (after a no-grad forward, after a training forward): None, or a tensor "plain" / with a "grad_fn"
+_LOSS_EXPECT = {"naive": (None, None), "switch": ("plain", "grad_fn"), "gshard": (None, "grad_fn"), "noisy": (None, "grad_fn")}
+
+
+def _loss_state(gate):
+    loss = gate.get_loss(clear=False)
+    if loss is None:
+        return None
+    assert torch.is_tensor(loss)
+    return "grad_fn" if loss.grad_fn is not None else "plain"
+
+
+def _gate_loss_worker(q):
+    """One-rank NCCL group: for every gate the loss state after every no-grad site (single rank, counted and static exchange) and
+    after one training forward, and ``last_plan`` of mod(x) against the counted expert-parallel forward under one seed."""
+    import socket
+    import torch.distributed as dist
+    from slim_switch_moe_vit_amd import ep
+    torch.cuda.set_device(0)
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=torch.device(DEV))
+    try:
+        T, d, h, E = 129, 192, 384, 4
+        x = torch.randn(T, d, generator=_gen(5)).to(DEV)
+        ln, ln2 = torch.nn.LayerNorm(d, eps=1e-6).to(DEV), torch.nn.LayerNorm(d, eps=1e-6).to(DEV)
+        skip_gate = sm.Gate(d, 1.0, target_threshold=0.55).to(DEV).eval()
+        res = {}
+        for name, (kind, k) in _LOSS_GATES.items():
+            torch.manual_seed(2)
+            mod = sm.FMoETransformerMLP(E, d, h, top_k=k, gate=kind).to(DEV).eval()
+            g = mod.gate
+            sites = {
+                "call": lambda: mod(x),
+                "forward_add": lambda: mod.forward_add(x, x),
+                "forward_norm_add": lambda: mod.forward_norm_add(x, ln),
+                "steps_tail": lambda: ep.drain(mod.forward_norm_add_steps(x.clone(), ln, tail=(197, 1))),
+                "steps_next_norm": lambda: ep.drain(mod.forward_norm_add_steps(x, ln, next_norm=ln2)),
+            }
+            if name == "naive":
+                with torch.no_grad():
+                    assert mod.norm_gate_fusable(x, ln)
+                sites["forward_norm_gate_add"] = lambda: mod.forward_norm_gate_add(x.clone().reshape(1, T, d), ln, skip_gate)
+            out = {"fresh": _loss_state(g), "nograd": {}, "plans_equal": None}
+            plans = {}
+            for mode in ("single", "counted", "static"):
+                mod.force_ep = mode != "single"
+                mod.ep_speculative = float(E) if mode == "static" else None     # (slots that hold every row: nothing overflows)
+                for site, fn in sites.items():
+                    if site == "forward_norm_gate_add" and mode == "static":
+                        continue
+                    # GShard / Noisy: a planted loss must be gone afterwards; Switch: start from None, so that what is found was set
+                    g.set_loss(torch.ones((), device=DEV) if _LOSS_EXPECT[name][0] is None and name != "naive" else None)
+                    torch.manual_seed(5)
+                    with torch.no_grad():
+                        if mode == "counted":
+                            with ep.dynamic_only():
+                                fn()
+                        else:
+                            fn()
+                    out["nograd"][f"{mode} {site}"] = _loss_state(g)
+                    if site == "call":
+                        plans[mode] = [t.clone() for t in mod.last_plan]
+                    ep.check_static_overflow(flush=True)
+            out["plans_equal"] = [bool(torch.equal(a, b)) for a, b in zip(plans["single"], plans["counted"])]
+            mod.force_ep = False
+            mod.train()
+            g.set_loss(None)
+            mod(x.clone().requires_grad_(True))
+            out["train"] = _loss_state(g)
+            res[name] = out
+        q.put(res)
+    finally:
+        torch.cuda.synchronize()
+        dist.destroy_process_group()
+
+
+def test_the_loss_a_gate_is_left_with_after_every_routing_site():
+    """Switch: a tensor without grad_fn after a no-grad forward, with one after a training forward; GShard / Noisy: None after a
+    no-grad forward (a loss planted before it is gone), a tensor with grad_fn in training; Naive: None everywhere.  Every no-grad
+    site -- mod(x), forward_add, forward_norm_add, forward_norm_add_steps with tail= / next_norm=, forward_norm_gate_add (naive) --
+    on a single rank and with force_ep on a one-rank group, counted and static exchange; and ``last_plan`` of mod(x) is the counted
+    expert-parallel forward's, tensor by tensor, under the same seed.  T = 129, d = 192, h = 384, E = 4."""
+    import torch.multiprocessing as mp
+    from _mp import join_or_kill
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_gate_loss_worker, args=(q,))
+    p.start()
+    join_or_kill([p], 300)
+    res = q.get(timeout=10)
+    print("gate loss state per site:", res)
+    assert set(res) == set(_LOSS_GATES)
+    for name, out in res.items():
+        nograd, train = _LOSS_EXPECT[name]
+        assert out["fresh"] is None, (name, out)
+        assert len(out["nograd"]) == (17 if name == "naive" else 15), (name, out)
+        for site, state in out["nograd"].items():
+            assert state == nograd, (name, site, state, nograd)
+        assert out["train"] == train, (name, out["train"], train)
+        assert len(out["plans_equal"]) == 6 and all(out["plans_equal"]), (name, out["plans_equal"])

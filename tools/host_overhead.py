@@ -19,7 +19,7 @@ def main():
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     args = argparse.Namespace(experts=8, compute_dtype="f16", gemm_variant=4, ep_chunks=1, force_ep=a.force_ep,
-                              no_cpu_baseline=True, ep_micro_batches=a.ep_micro_batches)
+                              no_cpu_baseline=True, ep_micro_batches=a.ep_micro_batches, compute_streams=1)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     if a.force_ep:
